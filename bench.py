@@ -1,7 +1,7 @@
 """Headline benchmark: sequences/sec of end-to-end global reconstruction (GlobalReconOptimizer.optimize_resident) on 300-frame,
 1-person, dynamic-camera synthetic sequences (BASELINE.json configs[1], cfg `glamr_dynamic`, 500 Adam iterations).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--mode weak|strong --total 64]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--mode weak|strong --total 64] [--seed S] [--dump-outputs DIR]
 
 A "step" = one pass of the hot path over one batch of B independent synthetic sequences per GPU: per-person preparation of the
 HybrIK arrays, motion infilling + trajectory prediction, SMPL skinning, scene initialisation and the full optimisation schedule.
@@ -377,6 +377,42 @@ def person_sharded_line(asset_root, dev, rank, world, iters=20, scenes=8, group=
                     'shared camera gradient and the Adam launch; the default keeps the scene in one workgroup for all iterations of a stage'}
 
 
+DUMP_SCENES = 64                              # --dump-outputs: scenes of the batch written out (a fixed, seeded sample when the batch is larger)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def step_outputs(model, packed, n_scenes, sample=DUMP_SCENES, seed=0):
+    """What a caller of optimize_resident receives -- the device arrays of `packed` that collect() cuts the result dictionaries from
+    (GlobalReconOptimizer._FETCH, the per-person arrays, the relative camera transforms of multi-person scenes, the latent draws) -- for a fixed, seeded sample
+    of the batch's scenes, as host arrays: float32 arrays as they are, integer ones as float64.  `scene_index` holds the sampled scenes."""
+    import numpy as np
+    import torch
+    idx = np.arange(n_scenes) if n_scenes <= sample else np.sort(np.random.RandomState(seed).choice(n_scenes, sample, replace=False))
+    src = {k: packed.t[k] for k in model._FETCH}
+    src.update({'pa_' + k: v for k, v in packed.person_arrays.items() if k not in ('nets_pose', 'nets_vis')})
+    if 'rel_transform_cam' in packed.t:
+        src['rel_transform_cam'] = packed.t['rel_transform_cam']
+    if getattr(packed, 'latents', None) is not None:
+        src['latent_motion'], src['latent_traj'] = packed.latents                       # the priors' draws this step was initialised with
+    sel = torch.as_tensor(idx, device=packed.device)
+    out = {'scene_index': idx.astype(np.float64)}
+    for k, v in src.items():
+        rows = v.reshape(n_scenes, -1, *v.shape[1:]) if v.shape[0] != n_scenes else v        # per-person arrays: (S * P, ...) -> (S, P, ...)
+        a = rows.index_select(0, sel).cpu().numpy()
+        out[k] = a if a.dtype == np.float32 else a.astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit('bench: --dump-outputs would write %d bytes (limit %d)' % (total, DUMP_MAX_BYTES))
+    return out
+
+
+def write_outputs(arrays, out_dir):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+
+
 HARD_EXIT = []      # reasons why this rank must leave without tearing its process group down (see `guarded`)
 
 
@@ -481,7 +517,14 @@ def run(argv=None):
     ap.add_argument('--no-early-prep', action='store_true', help='capture the pipelined step with the library\'s default cut (the whole batch behind the gate: two graphs per step)')
     ap.add_argument('--force-dist', action='store_true', help='create the process group also at --gpus 1 (a world of one rank): runs the init / barrier / reduction / '
                     'collective-latency code of the multi-GPU path on a single GPU (tests/test_e2e_gpu.py)')
+    ap.add_argument('--seed', type=int, default=0, help='seed of the generators the latent draws of the priors come from (rank r: seed + r); the same arguments, the same inputs')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write what the LAST timed step computed (rank 0: the arrays a caller of '
+                    'optimize_resident receives, for a fixed, seeded sample of %d scenes of the batch) as DIR/<name>.npy, float32 / float64' % DUMP_SCENES)
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and args.stub_model:
+        ap.error('--dump-outputs needs the real model')
 
     if args.gpus > 1 and 'RANK' not in os.environ:
         # launched plainly (`python bench.py --gpus N`): spawn the N ranks ourselves, one process per GPU, exactly as the driver's
@@ -491,6 +534,7 @@ def run(argv=None):
     import torch.distributed as dist
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
+    torch.manual_seed(args.seed + rank)                            # (unseeded, a process's default generators need not start alike)
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
     if world != args.gpus:
         raise SystemExit('--gpus %d inside a job of WORLD_SIZE=%d: launch with torch.distributed.run --nproc-per-node %d, or plainly (no RANK in the '
@@ -644,6 +688,13 @@ def run(argv=None):
     if use_dist:
         dist.barrier()
     elapsed = time.time() - t0
+    # --dump-outputs: the last timed step's results, copied before anything below runs on their buffers again (the replay check poisons them)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        last = step_graphs[(args.steps - 1) % len(step_graphs)].packed if step_graphs else keep[-1]
+        arrays = step_outputs(model, last, B)
+        write_outputs(arrays, args.dump_outputs)
+        dumped = {'dir': args.dump_outputs, 'scenes': len(arrays['scene_index']), 'arrays': sorted(arrays), 'bytes': sum(a.nbytes for a in arrays.values())}
     # What the timed region computed, checked after the clock has stopped (replay_check_of above): a difference is an error, no number is printed
     replay_check = None
     if step_graphs and on_gpu:
@@ -839,7 +890,7 @@ def run(argv=None):
                                       '2 single-stream plain steps right after the timed region: in the timed region the launches of the %d stream(s) '
                                       'share the CUs%s' % (len(streams), ' and are graph replays (one workspace per graph: no per-replay stamps)' if step_graphs else '')),
                          'note': 'traffic = memory-side bytes of one launch (rocprofv3 PMC passes on the shipped instance)'},
-            'replay_check': replay_check,
+            'replay_check': replay_check, 'dump_outputs': dumped,
             'pipeline': None if not coschedule else {
                 'coscheduled_streams': True, 'stage_launch_ms_alone': k_avg, 'stage_launch_ms_beside_the_priors': beside,
                 'critical_cycle': 'per batch and stream -- preparation (ahead of the gate: three-graph cut), infiller I beside the other batch\'s stage (~27 ms), then, when '
