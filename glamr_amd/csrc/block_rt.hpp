@@ -149,9 +149,7 @@ struct DeviceRT {
         if (lane == (reverse ? 0 : 63)) r[c * 16 + wave] = v;
         x[c] = v;
       }
-#if !defined(GLAMR_EXP_NOSYNC) || GLAMR_EXP_NOSYNC < 2
       __syncthreads();
-#endif
       // the wave totals of every channel are fetched with two vector reads per channel, all issued before the first is used (a workgroup has at
       // most 8 waves): walking them one ds_read at a time was up to 8 dependent LDS round trips per channel.  Same additions in the same order.
       for (int c = 0; c < nch; ++c) {
@@ -176,11 +174,7 @@ struct DeviceRT {
   }
   __device__ __forceinline__ int tid() const { return threadIdx.x; }
   __device__ __forceinline__ int nthreads() const { return blockDim.x; }
-#ifdef GLAMR_EXP_NOSYNC      // development aid (WRONG results): what the workgroup barriers of the iteration cost -- 1: rt.sync() only, 2: the scans' as well
-  __device__ __forceinline__ void sync() const {}
-#else
   __device__ __forceinline__ void sync() const { __syncthreads(); }
-#endif
   __device__ float reduce_sum(float v) const {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     __syncthreads();

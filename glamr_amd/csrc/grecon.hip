@@ -19,20 +19,14 @@
 namespace glamr {
 namespace GLAMR_GRECON_NS {
 
-#ifndef GLAMR_GRECON_MAX_THREADS
-#define GLAMR_GRECON_MAX_THREADS 512
-#endif
-constexpr int MAX_THREADS = GLAMR_GRECON_MAX_THREADS;
+constexpr int MAX_THREADS = 512;
 static_assert(MAX_THREADS <= 512, "DeviceRT::scan_multi / scan_regs fetch the wave totals of a workgroup as two float4 reads: at most 8 waves (block_rt.hpp)");
-#ifndef GLAMR_GRECON_WAVES_PER_EU
-#define GLAMR_GRECON_WAVES_PER_EU 2
-#endif
-#ifndef GLAMR_GRECON_LDS_KB
+constexpr int WAVES_PER_EU = 2;
+// the largest on-chip arena a stage launch asks for
 #ifdef GLAMR_GRECON_WIDE
-#define GLAMR_GRECON_LDS_KB 96      // (the description of 32 persons takes ~25 KB of static LDS)
+constexpr size_t LDS_MAX = 96 * 1024;      // (the description of 32 persons takes ~25 KB of static LDS)
 #else
-#define GLAMR_GRECON_LDS_KB 153
-#endif
+constexpr size_t LDS_MAX = 153 * 1024;
 #endif
 
 struct KernelArgs {
@@ -50,7 +44,7 @@ struct KernelArgs {
 };
 
 template <int FAST, bool SINGLE, int CAM, int TMC = 0>
-__global__ __launch_bounds__(MAX_THREADS, GLAMR_GRECON_WAVES_PER_EU) void grecon_stage_kernel(KernelArgs a) {
+__global__ __launch_bounds__(MAX_THREADS, WAVES_PER_EU) void grecon_stage_kernel(KernelArgs a) {
   __shared__ __attribute__((aligned(16))) float red[RT_RED_FLOATS];
   __shared__ Scene sc;
   __shared__ glamr_stage_desc s_st;        // the scene keeps POINTERS to these: they must live in LDS, not in a thread's private copy
@@ -59,12 +53,7 @@ __global__ __launch_bounds__(MAX_THREADS, GLAMR_GRECON_WAVES_PER_EU) void grecon
   const int si = blockIdx.x;
   // The stage is the pipeline's critical path; the priors' co-schedulable kernels of the other stream (nn_free.hpp) share these SIMDs
   // and have slack: this kernel's waves win the issue arbitration against them (user priority 0..3, the others stay at 0)
-#ifndef GLAMR_GRECON_PRIO
-#define GLAMR_GRECON_PRIO 3
-#endif
-#if !defined(GLAMR_GRECON_NO_SETPRIO) && GLAMR_GRECON_PRIO > 0
-  __builtin_amdgcn_s_setprio(GLAMR_GRECON_PRIO);
-#endif
+  __builtin_amdgcn_s_setprio(3);
   if (threadIdx.x == 0) {
     atomicMin(a.stamps, (unsigned long long)wall_clock64());
     s_st = a.st;
@@ -201,12 +190,7 @@ extern "C" int glamr_grecon_run_stage(const glamr_scene_batch* batch, const glam
   ka.grads_out = grads_out;
   int threads = (batch->max_len + 63) / 64 * 64;
   if (threads > MAX_THREADS) threads = MAX_THREADS;
-  if (const char* e = std::getenv("GLAMR_GRECON_THREADS_RT")) {      // development aid: fewer threads than frames = several passes per thread
-    const int cap = std::atoi(e);
-    if (cap >= 64 && cap < threads) threads = cap / 64 * 64;
-  }
   // on-chip arena: prefix-sum / neighbour-exchange arrays first, then as much of the compact keypoint table as fits
-  constexpr size_t LDS_MAX = GLAMR_GRECON_LDS_KB * 1024;
   size_t LDS_BUDGET = LDS_MAX;
   // Occupancy: a workgroup's waves hold 256 registers each, so a CU (4 SIMDs x 512 registers) takes 8 / waves workgroups -- if their arenas fit its
   // 160 KB together.  When the batch has more scenes than the chip has CUs, the arena is capped at that share (the keypoint table
@@ -220,7 +204,7 @@ extern "C" int glamr_grecon_run_stage(const glamr_scene_batch* batch, const glam
     if (n <= 0 && (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, devid_launch) != hipSuccess || n <= 0)) n = 256;
     return n;
   }();
-  const int wgs_per_cu = 4 * GLAMR_GRECON_WAVES_PER_EU / (threads / 64);
+  const int wgs_per_cu = 4 * WAVES_PER_EU / (threads / 64);
   // (the exchange arrays alone -- arena mode 3: parameters and Adam moments then stay in the workspace; keeping them on chip as well,
   // mode 1, needs 113 instead of 53 floats per frame and is what a scene that has its CU to itself gets)
   const size_t full_arena = scene_fast_floats(batch->max_persons, batch->max_len, 3) * sizeof(float);

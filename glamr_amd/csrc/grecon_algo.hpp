@@ -50,18 +50,6 @@ namespace GLAMR_GRECON_NS {
 constexpr int MAXP = GLAMR_MAX_PERSONS;
 
 constexpr int NJ = 26;
-#ifndef GLAMR_KP_DEPTH
-#define GLAMR_KP_DEPTH 3      // keypoint rows requested ahead of the one being processed (grecon_algo.hpp phase E; GLAMR_KP_GROUP=0 builds only)
-#endif
-#ifndef GLAMR_KP_FOLD
-// 1 (default since round 6): a keypoint row costs 43 instead of 52 VALU instructions (joint_nb: fused chains started from q, the robust term's constant
-// factors folded into the table's weight column, out-of-range rows through a zero weight) -- stage launch 21.7 -> 20.9 ms (profiles/r06_stage_ab.log).
-// The kernel is issue-bound on the SIMD that carries two of a scene's five waves, so its time follows the instruction count.  0 = rounds 4-5's arithmetic.
-#define GLAMR_KP_FOLD 1
-#endif
-#ifndef GLAMR_KP_GROUP
-#define GLAMR_KP_GROUP 3      // workspace keypoint rows per group (requested a whole group ahead, processed without branches); 0 = the one-row ring
-#endif
 constexpr float FPS = 30.0f;
 
 struct PersonConst {
@@ -238,44 +226,14 @@ GLAMR_HD void adam(float& p, float& m, float& v, float g, const AdamCoef& c) {
   p = p + rm::div_(c.neg_step * m, denom);
 }
 
-// N updates of one frame.  GLAMR_ADAM_INTERLEAVE (development aid, OFF): stage by stage across the N parameters, the scheduler barred from moving
-// anything across a stage boundary, so that every instruction of the ~30-long dependent chain of an update (through a square root and a
-// reciprocal) has N - 1 independent ones between itself and its consumer.  Measured on the MI355X (profiles/r05_stage_ab.log): 11.15 against
-// 10.8 us per iteration for the plain loop -- the scheduling barriers also pin the loads and stores around the updates, which costs more than
-// the shorter chains give.  Operation for operation what adam() does either way: same bits (tests/test_adam_exact.py, tools/stage_bits.py).
-#if defined(GLAMR_ADAM_INTERLEAVE) && GLAMR_ADAM_INTERLEAVE == 2      // the staged form WITHOUT scheduling barriers between the stages
-#define GLAMR_ADAM_STAGE_FENCE() ((void)0)
-#else
-#define GLAMR_ADAM_STAGE_FENCE() __builtin_amdgcn_sched_barrier(0)
-#endif
+// N updates of one frame, one after the other.  (Measured and dropped, round 5: stage by stage across the N parameters, the scheduler barred
+// from moving anything across a stage boundary, so that every instruction of the ~30-long dependent chain of an update (through a square root
+// and a reciprocal) has N - 1 independent ones between itself and its consumer -- 11.15 against 10.8 us per iteration for the plain loop on
+// the MI355X (profiles/r05_stage_ab.log): the scheduling barriers also pin the loads and stores around the updates, which costs more than the
+// shorter chains give.)
 template <int N>
 GLAMR_HD void adam_n(float (&P)[N], float (&M)[N], float (&V)[N], const float (&g)[N], const AdamCoef& c) {
-#if defined(__HIP_DEVICE_COMPILE__) && defined(GLAMR_ADAM_INTERLEAVE)
-  float s[N], den[N], num[N], y[N];
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    M[k] = rm::fma_(0.1f, g[k] - M[k], M[k]);
-    V[k] = rm::fma_(0.001f * g[k], g[k], V[k] * 0.999f);
-  }
-#pragma unroll
-  for (int k = 0; k < N; ++k) s[k] = rm::hw_sqrt_(V[k]);
-  GLAMR_ADAM_STAGE_FENCE();
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    const float a = rm::sqrt_rn_fix_(V[k], s[k]);
-    const float q = a * c.inv_bc2_sqrt;
-    den[k] = rm::fma_(rm::fma_(-c.bc2_sqrt, q, a), c.inv_bc2_sqrt, q) + 1e-8f;
-    num[k] = c.neg_step * M[k];
-  }
-  GLAMR_ADAM_STAGE_FENCE();
-#pragma unroll
-  for (int k = 0; k < N; ++k) y[k] = rm::hw_rcp_(den[k]);
-  GLAMR_ADAM_STAGE_FENCE();
-#pragma unroll
-  for (int k = 0; k < N; ++k) P[k] = P[k] + rm::div_fix_(num[k], den[k], y[k]);
-#else
   for (int k = 0; k < N; ++k) adam(P[k], M[k], V[k], g[k], c);
-#endif
 }
 
 GLAMR_HD void invert34(const float M[12], float O[12]) {       // [R|t] -> [R^T | -R^T t]   (inverse_transform)
@@ -832,25 +790,14 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
   static_assert(TMC == 0 || AF, "constant layouts are for single-person scenes with the full arena");
   const glamr_param_layout& lo = TMC > 0 ? OnChipLayout<TMC>::value : l;      // layout of the on-chip parameter / moment blocks
   // One-thread-per-frame instances with a compile-time geometry (TMC > 0: one person, TMC frames of layout, (TMC + 63) / 64 waves) carry a
-  // frame's scan operands and results, its trajectory row and the cos / sin of its heading in REGISTERS from phase to phase: the scans take and
-  // return registers (DeviceRT::scan_regs), `theta`, `xy` and `g_theta` are never stored, and phases B and C do not re-read what phase A wrote.
-  // GLAMR_REG_MASK (development aid) selects the pieces: 1 heading prefix sum, 2 the reverse phases' sums, 4 planar position, 8 the trajectory
-  // row, 16 cos / sin of the heading, 32 the camera parameters requested before the barrier that precedes phase D.  Default 23: pieces 8 and
-  // 32 are measured (the launch another 0.5 % shorter) and OFF, because they change results in the last bit: with a frame's 6D rotation
+  // frame's scan operands and results and the cos / sin of its heading in REGISTERS from phase to phase: the scans take and return registers
+  // (DeviceRT::scan_regs), and `theta`, `xy` and `g_theta` are never stored.  These pieces leave all outputs of all stages bit-identical to round 4's kernel (tools/stage_bits.py, seven cases,
+  // profiles/r05_stage_bits.log).  Two more were measured (the launch another 0.5 % shorter) and dropped, because they change results in the
+  // last bit: the trajectory row and the camera parameters requested before the barrier that precedes phase D.  With a frame's 6D rotation
   // arriving in registers instead of from LDS the compiler fuses a different product of rot6d_to_rotmat's `x0 x0 + x1 x1 + x2 x2` and
   // `b1 . a2` (which operand of a commutative node comes first is not stable under such edits), and the optimisation of a sequence with a
-  // detection gap is chaotic in exactly those bits.  Every enabled piece leaves all outputs of all stages bit-identical to
-  // round 4's kernel (tools/stage_bits.py, seven cases, profiles/r05_stage_bits.log).
-#ifndef GLAMR_REG_MASK
-#define GLAMR_REG_MASK 23
-#endif
+  // detection gap is chaotic in exactly those bits.
   constexpr bool REG_ANY = TMC > 0 && RT::one_thread_per_frame;
-  constexpr bool REG = REG_ANY && (GLAMR_REG_MASK & 1);          // heading prefix sum
-  constexpr bool REGB = REG_ANY && (GLAMR_REG_MASK & 2);
-  constexpr bool REG_XY = REG_ANY && (GLAMR_REG_MASK & 4);       // planar position prefix sum
-  constexpr bool REG_L = REG_ANY && (GLAMR_REG_MASK & 8);        // trajectory row
-  constexpr bool REG_CS = REG_ANY && (GLAMR_REG_MASK & 16);      // cos / sin of the heading
-  constexpr bool REG_CAM = REG_ANY && (GLAMR_REG_MASK & 32);     // camera parameters requested early
   constexpr int NWC = TMC > 0 ? (TMC + 63) / 64 : 1;
   // Uniform scalars of the scene description the loop needs (single-person instances): the description lives in LDS, which every phase
   // writes, so the compiler must re-read them -- a ds_read, a wait and two v_readfirstlane at the top of every phase -- unless they are
@@ -879,10 +826,13 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
   // launch of every iteration of the launch-by-launch schedules) stops after phase D: it needs neither the visibility tables nor the
   // normalisers nor the per-joint score sums -- 0.40 -> 0.2 ms of a launch that sits on the pipeline's critical chain (round 5).
   const bool poses_only = st.niters == 0 && (st.flags & GLAMR_FLAG_POSES_ONLY) && !cam_from_person;
-  // The keypoint row's arithmetic with folded constants (GLAMR_KP_FOLD, joint_nb) -- except where the camera rides on the person (cfg glamr_3dpw):
+  // The keypoint row's arithmetic with folded constants (joint_nb, round 6): a row costs 43 instead of 52 VALU instructions (fused chains started
+  // from q, the robust term's constant factors folded into the table's weight column, out-of-range rows through a zero weight) -- stage launch
+  // 21.7 -> 20.9 ms (profiles/r06_stage_ab.log); the kernel is issue-bound on the SIMD that carries two of a scene's five waves, so its time
+  // follows the instruction count.  Except where the camera rides on the person (cfg glamr_3dpw):
   // there the first Adam steps are lr x the SIGN of gradients that are rounding noise, the reference's sign is reproduced by rounds 4-5's operation
   // order (0.002 px after 15 steps against 0.20 px with any other: tests/grecon_common.py KSTEP_TOL), and that order is kept, as for the scans.
-  const bool kp_fold = GLAMR_KP_FOLD != 0 && !cam_from_person;
+  const bool kp_fold = !cam_from_person;
   // GLAMR_FLAG_KEEP_TABLES (launch-by-launch schedules, every gradient launch of a stage but its first, on the SAME workspace): what the stage set-up
   // leaves in the workspace and no iteration touches -- visibility tables, per-joint score sums, the orientation targets, the workspace rows of the
   // keypoint table -- is still there.  Honoured by the several-person run-time-layout instances only (see NR below: the others keep their code).
@@ -1077,8 +1027,7 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
     // reference's 15-step state to 0.002 px; the DPP order 0.20 px, and so does DPP with only the planar-position gradient's scan in the old
     // order: profiles/r05_gputest_a.log); every other instance runs the DPP scans.
     const bool scan_shuffle = cam_from_person;
-    // REG instances: this frame's row, heading prefix sum with its cos / sin, and planar position, carried in registers (lanes beyond T: zeros)
-    LocalRow Lr{};
+    // REG_ANY instances: this frame's heading prefix sum with its cos / sin, and planar position, carried in registers (lanes beyond T: zeros)
     float th_r[1] = {0.f}, cs_r = 1.f, sn_r = 0.f, xy_r[2] = {0.f, 0.f};
     for (int t = rt.tid(); frame_in(t, T); t += fstep)
       for (int p = 0; p < P; ++p) {
@@ -1088,13 +1037,12 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
           const LocalRow L = HOIST ? local_row_regs(fr.prior, fr.h_prior, fr.dmask, c.dheading_mask != nullptr, c.p, lo, t - c.fr_start)
                                    : local_row(c, lo, t - c.fr_start);
           store_row(pv(p).Lc, sh.TM, t, L);
-          if (REG_L) Lr = L;
           // atan2(sin h, cos h) of the reference (:401-405) only wraps h into (-pi, pi]: done arithmetically
           v = L.h - 6.28318530717958647692f * rintf(L.h * 0.15915494309189533577f);
         }
-        if (REG) th_r[0] = v; else pv(p).theta[t] = v;
+        if (REG_ANY) th_r[0] = v; else pv(p).theta[t] = v;
       }
-    if constexpr (REG) {
+    if constexpr (REG_ANY) {
       rt.template scan_regs<NWC, 1>(th_r, false, scan_shuffle);
     } else
 #ifdef GLAMR_GRECON_WIDE      // absolute_heading (:59,283,421): the per-frame headings are not summed up (traj_local2global_heading(local_heading=False))
@@ -1117,10 +1065,10 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
     for (int t = rt.tid(); frame_in(t, T); t += fstep)
       for (int p = 0; p < P; ++p) {
         float sn, cs;
-        rm::sincos_(REG ? th_r[0] : pv(p).theta[t], sn, cs);
+        rm::sincos_(REG_ANY ? th_r[0] : pv(p).theta[t], sn, cs);
         pv(p).csn[t * 2 + 0] = cs;
         pv(p).csn[t * 2 + 1] = sn;
-        if (REG_CS) { cs_r = cs; sn_r = sn; }
+        if (REG_ANY) { cs_r = cs; sn_r = sn; }
       }
     rt.sync();
     GLAMR_MARK(rt, 0);
@@ -1131,7 +1079,7 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
         float dx = 0.f, dy = 0.f;
         if (t >= c.fr_start && t < c.fr_end) {
           const int e = t - c.fr_start;
-          const LocalRow L = REG_L ? Lr : load_row(pv(p).Lc, sh.TM, t);
+          const LocalRow L = load_row(pv(p).Lc, sh.TM, t);
           dx = L.dx; dy = L.dy;
           // (neighbours' values are fetched with a clamped index, outside the per-lane condition: a load behind a condition cannot be
           // issued early or batched with others, and costs its own round trip -- here and in phases E3, E4 and I)
@@ -1142,21 +1090,12 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
             dy = L.dx * sn + L.dy * cs;
           }
         }
-        if (REG_XY) { xy_r[0] = dx; xy_r[1] = dy; } else {
+        if (REG_ANY) { xy_r[0] = dx; xy_r[1] = dy; } else {
           pv(p).xy[t * 2 + 0] = dx;
           pv(p).xy[t * 2 + 1] = dy;
         }
       }
-    // REG instances with an own camera per frame: this frame's camera parameters (written by this thread, in phase E5 of the previous
-    // iteration) are requested before the scan's barrier instead of in phase D, where nothing covered their latency
-    constexpr bool CAMPRE = REG_CAM && CAM == 1;
-    float cam9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (CAMPRE)
-      for (int t = rt.tid(); frame_in(t, T); t += fstep) {
-        for (int k = 0; k < 6; ++k) cam9[k] = sh.cp[lo.cam_rot6d + t * 6 + k];
-        for (int k = 0; k < 3; ++k) cam9[6 + k] = sh.cp[lo.cam_trans + t * 3 + k];
-      }
-    if constexpr (REG_XY) {
+    if constexpr (REG_ANY) {
       rt.template scan_regs<NWC, 2>(xy_r, false, scan_shuffle);
     } else {
       float* ch[16];
@@ -1179,12 +1118,12 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
         const PersonView& s = c;
         float c1[3], c2[3], tb[3], phi = 0.f;
         if (t >= c.fr_start && t < c.fr_end) {
-          const LocalRow L = REG_L ? Lr : load_row(s.Lc, sh.TM, t);
+          const LocalRow L = load_row(s.Lc, sh.TM, t);
           float Rl[9];
           rm::rot6d_to_rotmat(L.r6, Rl);
           for (int k = 0; k < 3; ++k) { c1[k] = Rl[k * 3 + 1]; c2[k] = Rl[k * 3 + 2]; }
-          phi = REG ? th_r[0] : s.theta[t];
-          tb[0] = REG_XY ? xy_r[0] : s.xy[t * 2 + 0]; tb[1] = REG_XY ? xy_r[1] : s.xy[t * 2 + 1]; tb[2] = L.z;
+          phi = REG_ANY ? th_r[0] : s.theta[t];
+          tb[0] = REG_ANY ? xy_r[0] : s.xy[t * 2 + 0]; tb[1] = REG_ANY ? xy_r[1] : s.xy[t * 2 + 1]; tb[2] = L.z;
         } else {
           float Rb[9];
           rm::aa_to_rotmat_k(c.base_orient + t * 3, Rb);
@@ -1193,7 +1132,7 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
         float sn = 0.f, cs = 1.f;
         const bool frozen = !SINGLE && c.frozen;            // the given pose already carries its owner's world heading offset
         if (has_wd && !frozen) { phi += s.p[lo.world_dheading + t]; rm::sincos_(phi, sn, cs); }
-        else if (t >= c.fr_start && t < c.fr_end) { cs = REG_CS ? cs_r : s.csn[t * 2 + 0]; sn = REG_CS ? sn_r : s.csn[t * 2 + 1]; }
+        else if (t >= c.fr_start && t < c.fr_end) { cs = REG_ANY ? cs_r : s.csn[t * 2 + 0]; sn = REG_ANY ? sn_r : s.csn[t * 2 + 1]; }
         float w1[3], w2[3];
         rotz2(cs, sn, c1, w1);
         rotz2(cs, sn, c2, w2);
@@ -1217,8 +1156,8 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
         if (var_cam) {
           const int row = fixed_cam ? 0 : t;
           float R[9];
-          rm::rot6d_to_rotmat(CAMPRE ? cam9 : sh.cp + lo.cam_rot6d + row * 6, R);
-          for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) M[i * 4 + j] = R[i * 3 + j]; M[i * 4 + 3] = CAMPRE ? cam9[6 + i] : sh.cp[lo.cam_trans + row * 3 + i]; }
+          rm::rot6d_to_rotmat(sh.cp + lo.cam_rot6d + row * 6, R);
+          for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) M[i * 4 + j] = R[i * 3 + j]; M[i * 4 + 3] = sh.cp[lo.cam_trans + row * 3 + i]; }
         } else {
           for (int k = 0; k < 12; ++k) M[k] = sh.cam_pose[(size_t)t * 12 + k];
         }
@@ -1420,9 +1359,6 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
             // the next joint's six values are fetched while the current one is processed (the rows that do not fit on chip come
             // from the workspace: hundreds of cycles each with one or two waves per SIMD to hide them)
             const int njc = s.njc, nf = s.njc_fast, TMs = sh.TM;
-            // A ring of KP_DEPTH joints in flight: a row from the workspace takes 300-400 ns to arrive and a joint ~120 ns to process
-            constexpr int KD = GLAMR_KP_DEPTH;
-            float nx[KD][6];
             // (two loops, one per memory: a pointer selected between the arena and the workspace would be a generic one -- flat loads
             // with 64-bit per-lane addresses that wait on both memory counters)
             auto fetch_chip = [&](int jj, float (&dst)[6]) {
@@ -1433,26 +1369,11 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
               const float* o = s.kpc_ws + (size_t)jj * 6 * TMs + t;
               for (int k = 0; k < 6; ++k) dst[k] = o[k * TMs];
             };
-            auto run = [&](int lo, int hi, auto fetch) {
-#pragma unroll
-              for (int d = 0; d < KD; ++d) if (lo + d < hi) fetch(lo + d, nx[d]);
-              for (int jj = lo; jj < hi; jj += KD) {
-#pragma unroll
-                for (int d = 0; d < KD; ++d) {
-                  if (jj + d >= hi) break;
-                  const float cur[6] = {nx[d][0], nx[d][1], nx[d][2], nx[d][3], nx[d][4], nx[d][5]};
-                  if (jj + d + KD < hi) fetch(jj + d + KD, nx[d]);
-                  if (cur[5] == 0.f) continue;
-                  joint(cur, cur[3], cur[4], cur[5], 0.f, -1);
-                }
-              }
-            };
-#if GLAMR_KP_GROUP > 0
-            // Workspace rows in GROUPS, the next group requested before the current one is processed, and no branch inside a group: around
-            // a loop back edge (or any merge) the compiler cannot count the loads in flight and waits for ALL of them -- with the one-row
-            // ring above every workspace row cost a full memory round trip (0.3 us); a whole group of arithmetic now covers it.
-            constexpr int KG = GLAMR_KP_GROUP;
-            (void)run;
+            // Workspace rows in GROUPS of KG, the next group requested before the current one is processed, and no branch inside a group: a row
+            // from the workspace takes 300-400 ns to arrive and a joint ~120 ns to process, and around a loop back edge (or any merge) the
+            // compiler cannot count the loads in flight and waits for ALL of them -- with a ring of rows in flight (rounds 4-5) every workspace
+            // row cost a full memory round trip (0.3 us); a whole group of arithmetic now covers it.
+            constexpr int KG = 3;
             if (w_kp != 0.f) {
               // Every multiply-add of a row is written out (fused where fma_ says so, nowhere else): the compiler contracts a * b + c at its
               // own discretion PER COPY of this code, and the copies (on-chip rows, the two group buffers) must agree to the bit -- which
@@ -1529,10 +1450,6 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
                 base += KG;
               }
             }
-#else
-            run(0, nf, fetch_chip);
-            run(nf, njc, fetch_ws);
-#endif
           }
           if (w_kp != 0.f && kp_frame) push_back();
         }
@@ -1722,7 +1639,7 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
     const float w_z = active(GLAMR_LOSS_LOCAL_Z_REG) ? st.loss_weight[GLAMR_LOSS_LOCAL_Z_REG] / n_exist : 0.f;
     const float w_dxy = active(GLAMR_LOSS_LOCAL_DXY_REG) ? st.loss_weight[GLAMR_LOSS_LOCAL_DXY_REG] / n_exist_m1 : 0.f;
     const float w_dh = active(GLAMR_LOSS_LOCAL_DHEADING_REG_NEW) ? st.loss_weight[GLAMR_LOSS_LOCAL_DHEADING_REG_NEW] / n_exist_m1 : 0.f;
-    float gth_r[1] = {0.f}, gxy_r[2] = {0.f, 0.f};      // REGB instances: this frame's heading / planar-position gradient (scan operands and results)
+    float gth_r[1] = {0.f}, gxy_r[2] = {0.f, 0.f};      // REG_ANY instances: this frame's heading / planar-position gradient (scan operands and results)
     for (int t = rt.tid(); frame_in(t, T); t += fstep)
       for (int p = 0; p < P; ++p) {
         const PersonView c = pv(p);
@@ -1747,7 +1664,7 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
         const float gw[1] = {gphi};
         if (!ex) {
           if (upd_wd) a_wd.step_store(s.p, s.m, s.v, sh.store_grad ? s.g : nullptr, lo.world_dheading + t, gw, ac);
-          if (!REGB) { s.g_theta[t] = 0.f; s.g_xy[t * 2 + 0] = 0.f; s.g_xy[t * 2 + 1] = 0.f; }
+          if (!REG_ANY) { s.g_theta[t] = 0.f; s.g_xy[t * 2 + 0] = 0.f; s.g_xy[t * 2 + 1] = 0.f; }
           continue;
         }
         const LocalRow L = load_row(s.Lc, sh.TM, t);
@@ -1762,7 +1679,7 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
           for (int r = 0; r < 3; ++r) { gRl[r * 3 + 0] = 0.f; gRl[r * 3 + 1] = gb2[r]; gRl[r * 3 + 2] = gb3[r]; }
           rm::rot6d_to_rotmat_bwd(L.r6, gRl, gr6);
         }
-        if (REGB) { gth_r[0] = gth; gxy_r[0] = s.g_tw[t * 3 + 0]; gxy_r[1] = s.g_tw[t * 3 + 1]; } else {
+        if (REG_ANY) { gth_r[0] = gth; gxy_r[0] = s.g_tw[t * 3 + 0]; gxy_r[1] = s.g_tw[t * 3 + 1]; } else {
           s.g_theta[t] = gth;
           s.g_xy[t * 2 + 0] = s.g_tw[t * 3 + 0];
           s.g_xy[t * 2 + 1] = s.g_tw[t * 3 + 1];
@@ -1788,7 +1705,7 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
       }
     GLAMR_MARK(rt, 14);
     if (update) {
-      if constexpr (REGB) {
+      if constexpr (REG_ANY) {
         rt.template scan_regs<NWC, 2>(gxy_r, true, scan_shuffle);
         for (int t = rt.tid(); frame_in(t, T); t += fstep) { pv(0).g_xy[t * 2 + 0] = gxy_r[0]; pv(0).g_xy[t * 2 + 1] = gxy_r[1]; }      // (frame t + 1's is read by frame t)
       } else {
@@ -1828,10 +1745,10 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
           const float csp = s.csn[tp * 2 + 0], snp = s.csn[tp * 2 + 1];
           if (e + 1 < n) {
             const float cs = cs0, sn = sn0;
-            if (REGB) gth_r[0] += gdx * (-Ln.dx * sn - Ln.dy * cs) + gdy * (Ln.dx * cs - Ln.dy * sn);
+            if (REG_ANY) gth_r[0] += gdx * (-Ln.dx * sn - Ln.dy * cs) + gdy * (Ln.dx * cs - Ln.dy * sn);
             else s.g_theta[t] += gdx * (-Ln.dx * sn - Ln.dy * cs) + gdy * (Ln.dx * cs - Ln.dy * sn);
           }
-          float gx = REGB ? gxy_r[0] : s.g_xy[t * 2 + 0], gy = REGB ? gxy_r[1] : s.g_xy[t * 2 + 1];
+          float gx = REG_ANY ? gxy_r[0] : s.g_xy[t * 2 + 0], gy = REG_ANY ? gxy_r[1] : s.g_xy[t * 2 + 1];
           if (e > 0) {
             const float cs = csp, sn = snp;
             const float a = gx * cs + gy * sn, b = -gx * sn + gy * cs;
@@ -1849,11 +1766,11 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
             if (upd_dxy) a_dxy.step_store(s.p, s.m, s.v, sh.store_grad ? s.g : nullptr, ixy, g2, ac);
           }
         }
-      // REGB instances: the state of this frame's heading parameter (own data) is requested before the scan's barrier, not after it
+      // REG_ANY instances: the state of this frame's heading parameter (own data) is requested before the scan's barrier, not after it
       AdamRegs<1> a_hpre;
       a_hpre.zero();
       float dmask_pre = 0.f;      // (and its row of the heading mask: a load from the workspace that sat right in front of its use)
-      if (REGB)
+      if (REG_ANY)
         for (int t = rt.tid(); frame_in(t, T); t += fstep) {
           const PersonView c = pv(0);
           if (t < c.fr_start || t >= c.fr_end) continue;
@@ -1863,7 +1780,7 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
           else a_hpre.P[0] = c.p[i];
           if (c.dheading_mask) dmask_pre = c.dheading_mask[e];
         }
-      if constexpr (REGB) {
+      if constexpr (REG_ANY) {
         rt.template scan_regs<NWC, 1>(gth_r, true, scan_shuffle);
       } else
 #ifdef GLAMR_GRECON_WIDE      // (absolute_heading: a frame's heading gradient is its own)
@@ -1890,20 +1807,20 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
           const PersonView& s = c;
           if (t < c.fr_start || t >= c.fr_end) continue;
           const int e = t - c.fr_start;
-          const float gh = REGB ? gth_r[0] : s.g_theta[t];
+          const float gh = REG_ANY ? gth_r[0] : s.g_theta[t];
           // frame 0 updates local_heading where the others update their row of local_dheading: selected index, one update (see phase I)
           const bool first = e == 0;
           const int i = first ? lo.local_heading : lo.local_dheading + e;
           const bool upd = first ? (bool)(st.var_mask & GLAMR_VAR_LOCAL_HEADING) : (bool)(st.var_mask & GLAMR_VAR_LOCAL_DHEADING);
           AdamRegs<1> a_h = a_hpre;
-          if (!REGB) { if (upd) a_h.load(s.p, s.m, s.v, i); else a_h.P[0] = s.p[i]; }
+          if (!REG_ANY) { if (upd) a_h.load(s.p, s.m, s.v, i); else a_h.P[0] = s.p[i]; }
           float gj[1] = {gh};
           if (!first) {
             const float v = a_h.P[0];
             float sv, cv;
             rm::sincos_(v, sv, cv);
             if (on(GLAMR_LOSS_LOCAL_DHEADING_REG_NEW)) { const float a = (cv - 1.0f) * FPS, b = sv * FPS; if (last) lsum[GLAMR_LOSS_LOCAL_DHEADING_REG_NEW] += a * a + b * b; }
-            const float mk = REGB ? dmask_pre : (c.dheading_mask ? c.dheading_mask[e] : 0.0f);
+            const float mk = REG_ANY ? dmask_pre : (c.dheading_mask ? c.dheading_mask[e] : 0.0f);
             const float g = (c.dheading_mask ? gh * mk : 0.0f) + 2.0f * FPS * FPS * ((cv - 1.0f) * (-sv) + sv * cv) * w_dh;
             gj[0] = g;
           }

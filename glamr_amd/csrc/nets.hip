@@ -277,47 +277,6 @@ __global__ __launch_bounds__(256) void fk_joints_kernel(const float* pose, int T
   if (j > 0) for (int c = 0; c < 3; ++c) xo[(j - 1) * 3 + c] = sP[fl][j][c] - sP[fl][0][c];
   else for (int c = 69; c < XLD; ++c) xo[c] = 0.0f;
 }
-// The same chain without LDS (co-schedulable, see nn_free.hpp): two frames per wave, lane = (frame, joint); a joint fetches its parent's
-// transform with twelve lane exchanges per tree level instead of reading it from LDS.  Same arithmetic in the same order.
-__global__ __launch_bounds__(64) void fk_joints_free_kernel(const float* pose, int Tpad, int max_len, const int* lens, const float* rest, const int32_t* parents, float* x) {
-  const int b = blockIdx.x, lane = threadIdx.x, fl = lane >> 5, j = lane & 31;
-  const int t = blockIdx.y * 2 + fl;
-  const bool joint = j < 24;
-  const bool active = joint && t < max_len && t < lens[b];
-  const int pa = joint ? parents[j] : -1;
-  int lev = 0;
-  if (joint) for (int a = pa; a >= 0; a = parents[a]) ++lev;
-  int nlev = lev;
-  for (int off = 32; off > 0; off >>= 1) nlev = max(nlev, __shfl_xor(nlev, off));
-  float R[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, G[9], P[3] = {0.f, 0.f, 0.f}, d[3] = {0.f, 0.f, 0.f};
-  if (active) {
-    if (j == 0) { const float z[3] = {0.f, 0.f, 0.f}; rm::aa_to_rotmat_s(z, R); }
-    else rm::aa_to_rotmat_s(pose + ((size_t)b * Tpad + t) * XLD + (j - 1) * 3, R);
-    if (j == 0) for (int c = 0; c < 3; ++c) P[c] = rest[c];
-    else for (int c = 0; c < 3; ++c) d[c] = rest[j * 3 + c] - rest[pa * 3 + c];
-  }
-  for (int e = 0; e < 9; ++e) G[e] = R[e];
-  const int src = (lane & 32) + max(pa, 0);
-  for (int L = 1; L <= nlev; ++L) {
-    float pg[9], pp[3];
-    for (int e = 0; e < 9; ++e) pg[e] = __shfl(G[e], src);
-    for (int c = 0; c < 3; ++c) pp[c] = __shfl(P[c], src);
-    if (active && lev == L) {
-      float o[3];
-      rm::mat3_mul(pg, R, G);
-      rm::mat3_vec(pg, d, o);
-      for (int c = 0; c < 3; ++c) P[c] = pp[c] + o[c];
-    }
-  }
-  const int root = lane & 32;
-  float p0[3];
-  for (int c = 0; c < 3; ++c) p0[c] = __shfl(P[c], root);
-  if (!joint || t >= max_len) return;
-  float* xo = x + ((size_t)b * max_len + t) * XLD;
-  if (!active) { for (int c = j * 4; c < j * 4 + 4; ++c) xo[c] = 0.0f; return; }
-  if (j > 0) for (int c = 0; c < 3; ++c) xo[(j - 1) * 3 + c] = P[c] - p0[c];
-  else for (int c = 69; c < XLD; ++c) xo[c] = 0.0f;
-}
 __global__ void masked_mean_kernel(const float* ctx, int max_len, const int* lens, float* mean, int frag = 0) {   // [B][max_len][256] -> [B][256]
   const int b = blockIdx.x, n = lens[b];
   for (int k = blockIdx.y * blockDim.x + threadIdx.x; k < D; k += blockDim.x * gridDim.y) {
@@ -470,33 +429,26 @@ int ln(hipStream_t st, const float* X, const float* R, const LN& n, float* Y, in
   hipLaunchKernelGGL(add_layernorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, X, R, n.g, n.b, Y, rows, D);
   return GLAMR_OK;
 }
-// rows from which the fused row-block / fused attention kernels (and, beside a stage, the co-schedulable ones) are used; below it the separate
-// small-M fp32 kernels.  GLAMR_NETS_FUSE_MIN_ROWS overrides it (development aid / A-B runs; read once)
-static const int FUSE_MIN_ROWS = [] { const char* e = std::getenv("GLAMR_NETS_FUSE_MIN_ROWS"); return e ? std::atoi(e) : 2048; }();
-inline bool fuse_attention(int M) {
-  static const bool no_fuse = std::getenv("GLAMR_NETS_NO_FUSE_ATTN") != nullptr || std::getenv("GLAMR_NETS_NO_FUSE") != nullptr;      // development aid
-  return !no_fuse && !tl_fp32 && !tl_free && M >= FUSE_MIN_ROWS;
-}      // below this the launches are latency-bound either way: separate small-M kernels
+// the fused row-block / fused attention kernels from SMALL_ROWS rows on (nn_kernels.hpp); below it the launches are latency-bound either way:
+// separate small-M fp32 kernels
+inline bool fuse_attention(int M) { return !tl_fp32 && !tl_free && M >= SMALL_ROWS; }
 // Y = LayerNorm(X W^T + b + R): attention out-projection + residual + norm in one pass over the rows
 int proj_ln(hipStream_t st, const Lin& L, const LN& n, const float* X, const float* R, float* Y, float* tmp, int M);
 // Y = [LayerNorm](act2(relu(X W1^T + b1) W2^T + b2) [+ R]): feed-forward block / two-layer MLP with the hidden rows on chip
 int mlp2(hipStream_t st, const Lin& L1, const Lin& L2, const LN* n, const float* X, int ldx, const float* R, float* Y, float* hidden, float* tmp, int M,
-         int act2, int xl = -1);
+         int act2);
 
 // Few rows (a window of one sequence has 50: the latent-optimisation mode makes ~335 such products forward and ~335 backward per iteration):
-// gemm_kernel walks K with v_mfma_f32_32x32x2_f32 on ONE accumulator per wave -- a chain of K / 2 dependent 64-cycle instructions, 3.4 us at
+// the fp32 GEMM of round 5 walked K with v_mfma_f32_32x32x2_f32 on ONE accumulator per wave -- a chain of K / 2 dependent 64-cycle instructions, 3.4 us at
 // K = 256 and 6.8 at 512 inside a 12 us kernel.  The one-wave split-fp16 kernel of nn_free.hpp (three v_mfma_f32_32x32x16_f16 per 16 k on two
 // column tiles, operands one step ahead, no LDS, no barrier) does the same product in 1.3 / 2.6 us of matrix time, on row-major rows as they are.
 // It takes the BACKWARD products (lin_bwd: gradient rows times transposed weights; 12.8 -> 11.2 ms per iteration of the mode).  The forward
 // products of few rows stay on the fp32 instruction: with them on the split kernel as well the mode runs at 10.5 ms, but the first gradient of
 // the motion latent moves by 3.8e-6 of its largest entry and, eight Adam steps later, the latent of one of the three reference fixtures is 9.5e-4
 // away instead of 1.4e-6 (Adam's first steps are sign-like: an entry whose gradient is ~0 takes a full step the other way) -- outside the 1e-4
-// tests/test_latent_gpu.py holds it to.  GLAMR_GEMM_SMALL_SPLIT_FWD=1 selects that variant, GLAMR_GEMM_SMALL_FP32=1 the fp32 kernel throughout.
+// tests/test_latent_gpu.py holds it to.
 inline bool small_rows_split(const Lin& L, int M, int ldx, int ldy, int ldr, int ldrb, bool bwd) {
-  static const bool keep_fp32 = std::getenv("GLAMR_GEMM_SMALL_FP32") != nullptr || std::getenv("GLAMR_GEMM_FP32_MFMA") != nullptr;
-  static const bool fwd_too = std::getenv("GLAMR_GEMM_SMALL_SPLIT_FWD") != nullptr;
-  if (!bwd && !fwd_too) return false;
-  return !keep_fp32 && !tl_fp32 && L.Ws && M > 0 && M < 2048 && L.K % 32 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldr % 4 == 0 && ldrb % 4 == 0;
+  return bwd && !tl_fp32 && L.Ws && M > 0 && M < SMALL_ROWS && L.K % 32 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldr % 4 == 0 && ldrb % 4 == 0;
 }
 
 int lin(hipStream_t st, const Lin& L, const float* X, int ldx, float* Y, int ldy, int M, int act = ACT_NONE, const float* R = nullptr, int ldr = 0,
@@ -522,11 +474,9 @@ int lin(hipStream_t st, const Lin& L, const float* X, int ldx, float* Y, int ldy
 }
 
 int proj_ln(hipStream_t st, const Lin& L, const LN& n, const float* X, const float* R, float* Y, float* tmp, int M) {
-  static const bool no_fuse = std::getenv("GLAMR_NETS_NO_FUSE") != nullptr;      // development aid: the separate GEMM + LayerNorm launches
-  if (!no_fuse && !tl_free && M >= FUSE_MIN_ROWS && L.N == D && L.K == D && L.Ws)
+  if (!tl_free && M >= SMALL_ROWS && L.N == D && L.K == D && L.Ws)
     return launch_rows(st, X, D, M, D, nullptr, 0, nullptr, nullptr, 1, 0, L.Ws, (size_t)D * L.K, L.K, L.b, ACT_NONE, R, D, n.g, n.b, Y, D);
-  static const bool res_in_ln = std::getenv("GLAMR_NETS_RES_IN_LN") != nullptr;      // development aid (A/B)
-  if (tl_free && !res_in_ln) {      // the residual in the GEMM's epilogue (same sum, same order): the three-pass LayerNorm then streams ONE array
+  if (tl_free) {      // the residual in the GEMM's epilogue (same sum, same order): the three-pass LayerNorm then streams ONE array
     RC(lin(st, L, X, D, tmp, D, M, ACT_NONE, R, D));
     return ln(st, tmp, nullptr, n, Y, M);
   }
@@ -534,15 +484,13 @@ int proj_ln(hipStream_t st, const Lin& L, const LN& n, const float* X, const flo
   return ln(st, tmp, R, n, Y, M);
 }
 int mlp2(hipStream_t st, const Lin& L1, const Lin& L2, const LN* n, const float* X, int ldx, const float* R, float* Y, float* hidden, float* tmp, int M,
-         int act2, int xl) {
-  static const bool no_fuse = std::getenv("GLAMR_NETS_NO_FUSE") != nullptr;
-  if (!no_fuse && !tl_free && M >= FUSE_MIN_ROWS && L1.N == FF && L2.N == D && L2.K == FF && L1.K <= D && L1.Ws && L2.Ws)
+         int act2) {
+  if (!tl_free && M >= SMALL_ROWS && L1.N == FF && L2.N == D && L2.K == FF && L1.K <= D && L1.Ws && L2.Ws)
     return launch_rows(st, X, ldx, M, L1.K, L1.Ws, (size_t)FF * L1.K, L1.b, nullptr, 1, 0, L2.Ws, (size_t)D * L2.K, L2.K, L2.b, act2, R, D,
                        n ? n->g : nullptr, n ? n->b : nullptr, Y, D);
-  RC(lin(st, L1, X, ldx, hidden, FF, M, ACT_RELU, nullptr, 0, nullptr, 1, 0, xl));
+  RC(lin(st, L1, X, ldx, hidden, FF, M, ACT_RELU));
   if (!n) return lin(st, L2, hidden, FF, Y, D, M, act2, R, D);
-  static const bool res_in_ln2 = std::getenv("GLAMR_NETS_RES_IN_LN") != nullptr;
-  if (tl_free && !res_in_ln2) {
+  if (tl_free) {      // (the residual in the GEMM's epilogue, as in proj_ln)
     RC(lin(st, L2, hidden, FF, tmp, D, M, act2, R, D));
     return ln(st, tmp, nullptr, *n, Y, M);
   }
@@ -1081,13 +1029,12 @@ void bilstm(glamr_nets* h, hipStream_t st, const float* G, float* const hh[2], c
 int traj_pass(glamr_nets* h, hipStream_t st, Ws& w, int B, int max_len, const int* lens_run, int mode, const float* eps, float* q_out, float* p_out,
               const float* init, int ldinit, float* out_orig, float* out_local, float* out_trans, float* out_orient, float* out_orient_q) {
   const int MT = B * max_len;
-  RC(mlp2(st, h->t_in1, h->t_in2, nullptr, w.tx, XLD, nullptr, w.th, w.tg, w.tq, MT, ACT_RELU, 0));      // (joint rows: row-major)
+  RC(mlp2(st, h->t_in1, h->t_in2, nullptr, w.tx, XLD, nullptr, w.th, w.tg, w.tq, MT, ACT_RELU));
   for (int l = 0; l < 2; ++l) {
-    RC(lin(st, h->t_ih[l], w.th, D, w.tg, 1024, MT, ACT_NONE, nullptr, 0, nullptr, 1, 0, l == 0 ? -1 : 0, 0));      // the recurrence reads and writes row-major rows
-    tl_free = 0;                                                   // from the first recurrence on: the LDS kernels (see enqueue_infer; restored by the caller)
+    RC(lin(st, h->t_ih[l], w.th, D, w.tg, 1024, MT));
     bilstm(h, st, w.tg, h->t_hh[l], lens_run, w.th, max_len, B);
   }
-  RC(mlp2(st, h->t_out1, h->t_out2, nullptr, w.th, D, nullptr, w.th, w.tg, w.tq, MT, ACT_RELU, 0));       // context [B][max_len][256]
+  RC(mlp2(st, h->t_out1, h->t_out2, nullptr, w.th, D, nullptr, w.th, w.tg, w.tq, MT, ACT_RELU));       // context [B][max_len][256]
   if (mode != GLAMR_VAE_INFER) {
     // posterior (DataEncoder.forward :160-199): [t_h, aa(q_h)] -> in_mlp -> 2 bi-LSTM -> out_mlp; fused with the context, mean over time
     RC(lin(st, h->te_in1, w.e6, 32, w.tg, FF, MT, ACT_RELU));
@@ -1105,26 +1052,25 @@ int traj_pass(glamr_nets* h, hipStream_t st, Ws& w, int B, int max_len, const in
     RC(lin(st, h->te_qz, w.tmean, D, w.tqz, D, B));
     if (q_out) GLAMR_HIP_CHECK(hipMemcpyAsync(q_out, w.tqz, (size_t)B * D * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
-  hipLaunchKernelGGL(masked_mean_kernel, dim3(B, 4), dim3(64), 0, st, w.th, max_len, lens_run, w.tmean, tl_free);
-  RC(lin(st, h->t_pr1, w.tmean, D, w.trow, FF, B, ACT_RELU, nullptr, 0, nullptr, 1, 0, 0, 0));      // one row per sequence: row-major throughout
-  RC(lin(st, h->t_pr2, w.trow, FF, w.tmean, D, B, ACT_RELU, nullptr, 0, nullptr, 1, 0, 0, 0));
-  RC(lin(st, h->t_pz, w.tmean, D, w.pz, D, B, ACT_NONE, nullptr, 0, nullptr, 1, 0, 0, 0));
+  hipLaunchKernelGGL(masked_mean_kernel, dim3(B, 4), dim3(64), 0, st, w.th, max_len, lens_run, w.tmean);
+  RC(lin(st, h->t_pr1, w.tmean, D, w.trow, FF, B, ACT_RELU));
+  RC(lin(st, h->t_pr2, w.trow, FF, w.tmean, D, B, ACT_RELU));
+  RC(lin(st, h->t_pz, w.tmean, D, w.pz, D, B));
   if (p_out) GLAMR_HIP_CHECK(hipMemcpyAsync(p_out, w.pz, (size_t)B * D * sizeof(float), hipMemcpyDeviceToDevice, st));
   if (mode == GLAMR_VAE_INFER) hipLaunchKernelGGL(reparam_traj_kernel, dim3(B), dim3(64), 0, st, w.pz, eps, w.z);
   else if (mode == GLAMR_VAE_TRAIN) hipLaunchKernelGGL(reparam_traj_kernel, dim3(B), dim3(64), 0, st, w.tqz, eps, w.z);
   else hipLaunchKernelGGL(mode_traj_kernel, dim3(B), dim3(NZ), 0, st, w.tqz, w.z);
-  RC(lin(st, h->t_dz, w.z, NZ, w.trow, FF, B, ACT_NONE, nullptr, 0, nullptr, 1, 0, 0, 0));      // W_z z + b, one row per sequence
+  RC(lin(st, h->t_dz, w.z, NZ, w.trow, FF, B));      // W_z z + b, one row per sequence
   // decoder MLP: relu(W_ctx ctx + [W_z z + b] of the sequence) -> relu(W_2 .): as ONE row-block launch (the 512-wide hidden rows stay in LDS:
-  // 629 MB less written and read again per 1024 x 300 frames); GLAMR_NETS_NO_FUSE keeps the two GEMMs
-  static const bool no_fuse_dec = std::getenv("GLAMR_NETS_NO_FUSE") != nullptr || std::getenv("GLAMR_NETS_NO_FUSE_DEC") != nullptr;
-  if (!no_fuse_dec && !tl_free && !tl_fp32 && MT >= FUSE_MIN_ROWS && max_len >= 64 && h->t_dctx.Ws && h->t_d2.Ws && h->t_dctx.K == D && h->t_dctx.N == FF && h->t_d2.K == FF && h->t_d2.N == D) {
+  // 629 MB less written and read again per 1024 x 300 frames)
+  if (!tl_fp32 && MT >= SMALL_ROWS && max_len >= 64 && h->t_dctx.Ws && h->t_d2.Ws && h->t_dctx.K == D && h->t_dctx.N == FF && h->t_d2.K == FF && h->t_d2.N == D) {
     RC(launch_rows(st, w.th, D, MT, D, h->t_dctx.Ws, (size_t)FF * D, h->t_dctx.b, w.trow, max_len, FF, h->t_d2.Ws, (size_t)D * FF, FF, h->t_d2.b, ACT_RELU,
                    nullptr, D, nullptr, nullptr, w.tq, D));
   } else {
     RC(lin(st, h->t_dctx, w.th, D, w.tg, FF, MT, ACT_RELU, nullptr, 0, w.trow, max_len, FF));
     RC(lin(st, h->t_d2, w.tg, FF, w.tq, D, MT, ACT_RELU));
   }
-  RC(lin(st, h->t_dfc, w.tq, D, w.traw, 64, MT, ACT_NONE, nullptr, 0, nullptr, 1, 0, -1, 0));
+  RC(lin(st, h->t_dfc, w.tq, D, w.traw, 64, MT));
   if (out_orig) hipLaunchKernelGGL(rows_out_kernel, dim3(MT), dim3(64), 0, st, w.traw, 64, MT, 11, out_orig);
   hipLaunchKernelGGL(traj_to_global2_kernel, dim3(B), dim3(256), 0, st, w.traw, 64, max_len, lens_run, init, ldinit, 1, out_local, out_trans, out_orient,
                      out_orient_q, w.tscr);
@@ -1149,21 +1095,12 @@ int enqueue_infer(glamr_nets* h, hipStream_t st, Ws& w, int B, int max_len, int 
   if (out_pose) hipLaunchKernelGGL(pose_out_kernel, dim3(B, max_len), dim3(64), 0, st, w.pose, max_len, w.Tpad, w.lens, out_pose);
   if (!do_traj) return GLAMR_OK;
   // ---- trajectory predictor -----------------------------------------------------------------------------------------------------
-  // The recurrence cannot do without LDS (W_hh does not fit a wave's registers and an L2 round trip per k step is 30 x the matrix time), so the
-  // chain stops at the first LSTM launch until the other stream's stage has retired: everything BEFORE it stays co-schedulable (it runs in
-  // the slack the infiller leaves beside the stage), everything from it on takes the LDS kernels, the faster ones on an empty GPU (traj_pass).
-  struct Restore { int v; ~Restore() { tl_free = v; } } restore{tl_free};
-  // Round 5: the WHOLE predictor on the LDS kernels, also what precedes its first recurrence (forward kinematics, input MLP, first input
+  // The WHOLE predictor runs on the LDS kernels (round 5), also what precedes its first recurrence (forward kinematics, input MLP, first input
   // projection: 1.9 ms on the LDS-free kernels, 1.2 on these).  Rounds 3 - 4 kept that prefix co-schedulable to use the slack beside the other
   // stream's stage; with the stage launch (27 ms beside the priors) now shorter than the infiller beside it (29 ms) the prefix starts when the
   // stage has just retired and finds an empty GPU: 37.9 -> 37.2 ms per step, alternated twice on one box (profiles/r05_pipeline_experiments.log).
-  // GLAMR_NETS_TRAJ_LDS=0 restores the co-schedulable prefix (for workloads whose stage outlasts the infiller).
-  static const bool traj_lds = [] { const char* e = std::getenv("GLAMR_NETS_TRAJ_LDS"); return !(e && e[0] == '0'); }();
-  if (traj_lds) tl_free = 0;
-  if (tl_free) {
-    hipLaunchKernelGGL(fk_joints_free_kernel, dim3(B, (max_len + 1) / 2), dim3(64), 0, st, w.pose, w.Tpad, max_len, w.lens, h->rest_joints, h->parents, w.tx);
-    return traj_pass(h, st, w, B, max_len, w.lens, GLAMR_VAE_INFER, traj_eps, nullptr, nullptr, nullptr, 0, nullptr, out_local_traj, out_trans, out_orient, nullptr);
-  }
+  struct Restore { int v; ~Restore() { tl_free = v; } } restore{tl_free};      // (a second enqueue after a failed capture starts from the same mode)
+  tl_free = 0;
   hipLaunchKernelGGL(fk_joints_kernel, dim3(B, (max_len + FK_FRAMES - 1) / FK_FRAMES), dim3(256), 0, st, w.pose, w.Tpad, max_len, w.lens, h->rest_joints, h->parents, w.tx);
   return traj_pass(h, st, w, B, max_len, w.lens, GLAMR_VAE_INFER, traj_eps, nullptr, nullptr, nullptr, 0, nullptr, out_local_traj, out_trans, out_orient, nullptr);
 }
@@ -1186,7 +1123,7 @@ extern "C" int glamr_nets_infer(glamr_nets* h, int B, int max_len, const int32_t
   GLAMR_REQUIRE(!do_infill || n_win <= n_win_max, "motion_eps holds %d windows per sequence, %d needed", n_win_max, n_win);
   hipStream_t st = static_cast<hipStream_t>(stream_);
   tl_fp32 = h->fp32_only ? 1 : 0;
-  tl_free = (!tl_fp32 && free_wanted(flags) && (size_t)B * WIN >= (size_t)FUSE_MIN_ROWS) ? 1 : 0;
+  tl_free = (!tl_fp32 && free_wanted(flags) && (size_t)B * WIN >= (size_t)SMALL_ROWS) ? 1 : 0;
   Ws w = ws_layout(B, max_len, static_cast<char*>(workspace));
   // A caller that is CAPTURING this stream (its whole step as one graph) gets the plain launch sequence recorded into its graph,
   // INCLUDING the upload of the lengths: they are copied to a pinned table the handle owns (alive until glamr_nets_destroy), and the
@@ -1203,11 +1140,10 @@ extern "C" int glamr_nets_infer(glamr_nets* h, int B, int max_len, const int32_t
     std::memcpy(pinned, lens_host, (size_t)B * sizeof(int32_t));
     lens_src = pinned;
   }
-  // Recorded into a caller's graph the upload is a KERNEL reading the pinned table (hipHostMalloc memory is device-visible); GLAMR_NETS_LENS_MEMCPY=1
-  // records a copy node instead.  (Round 5 blamed copy nodes at the start of a graph for the two-stream corruption; round 6 found the cause
-  // elsewhere -- packed-fp32 instructions, glamr_amd/build.py -- and both forms replay bit-identically: profiles/r06_pipeline_corruption.log.)
-  static const bool lens_memcpy = std::getenv("GLAMR_NETS_LENS_MEMCPY") != nullptr;
-  if (outer_capture && !lens_memcpy) hipLaunchKernelGGL(copy_ints_kernel, dim3((B + 255) / 256), dim3(256), 0, st, w.lens, lens_src, B);
+  // Recorded into a caller's graph the upload is a KERNEL reading the pinned table (hipHostMalloc memory is device-visible).  (Round 5 blamed
+  // copy nodes at the start of a graph for the two-stream corruption; round 6 found the cause elsewhere -- packed-fp32 instructions,
+  // glamr_amd/build.py -- and a copy node replays bit-identically: profiles/r06_pipeline_corruption.log.)
+  if (outer_capture) hipLaunchKernelGGL(copy_ints_kernel, dim3((B + 255) / 256), dim3(256), 0, st, w.lens, lens_src, B);
   else GLAMR_HIP_CHECK(hipMemcpyAsync(w.lens, lens_src, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
   auto enqueue = [&]() -> int {
     return enqueue_infer(h, st, w, B, max_len, n_win, n_win_max, do_infill, do_traj, body_pose, visible, motion_eps, traj_eps, out_pose, out_local_traj, out_trans,
@@ -1216,8 +1152,7 @@ extern "C" int glamr_nets_infer(glamr_nets* h, int B, int max_len, const int32_t
   // A batch is ~450 kernel launches.  The same call (same geometry, same buffers -- a caching allocator hands the same blocks back in
   // steady state) seen twice is captured into a HIP graph and replayed from then on: one launch on the host instead of 450, which is
   // what keeps the step time when the host is slow or shared.  Anything unexpected falls back to the plain launches.
-  static const bool no_graph = std::getenv("GLAMR_NETS_NO_GRAPH") != nullptr;
-  if (!no_graph && !outer_capture) {
+  if (!outer_capture) {
     glamr_nets::GraphKey key;
     std::memset(&key, 0, sizeof(key));
     key.v[0] = B; key.v[1] = max_len; key.v[2] = n_win; key.v[3] = flags | (tl_free << 16); key.v[4] = n_win_max;
@@ -1250,10 +1185,8 @@ extern "C" int glamr_nets_infer(glamr_nets* h, int B, int max_len, const int32_t
           (void)hipGetLastError();                       // not capturable: clear the error, keep the plain launches for this key
         } else {
           const int rc = enqueue();
-          const hipError_t e_in = hipPeekAtLastError();
           hipGraph_t g = nullptr;
           const hipError_t ec = hipStreamEndCapture(st, &g);
-          if (std::getenv("GLAMR_DEBUG_GRAPH")) std::fprintf(stderr, "graph capture: rc=%d in-capture error=%s end=%s B=%d max_len=%d flags=%d\n", rc, hipGetErrorString(e_in), hipGetErrorString(ec), B, max_len, flags);
           hipGraphExec_t exec = nullptr;
           if (rc == GLAMR_OK && ec == hipSuccess && g && hipGraphInstantiate(&exec, g, nullptr, nullptr, 0) == hipSuccess) {
             (void)hipGraphDestroy(g);

@@ -81,11 +81,7 @@ __global__ __launch_bounds__(64, MAXW) void gemm_free_kernel(GemmArgs a) {
   auto step = [&](int slot) {
     const float x[8] = {xr[slot][0][0], xr[slot][0][1], xr[slot][0][2], xr[slot][0][3], xr[slot][1][0], xr[slot][1][1], xr[slot][1][2], xr[slot][1][3]};
     f16x8 xh, xl;
-#ifdef GLAMR_GEMM_NOSPLIT      // development aid (tools/gemm_free_bench.py): what the operand split costs beside the stage -- wrong results
-    xh = __builtin_bit_cast(f16x8, xr[slot][0]); xl = __builtin_bit_cast(f16x8, xr[slot][1]);
-#else
     split8(x, xh, xl);
-#endif
     // the two small products first; consecutive MFMAs go to different accumulators
 #pragma unroll
     for (int j = 0; j < C; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wr[slot][1][j]), xh, acc[j], 0, 0, 0);
@@ -198,13 +194,10 @@ inline int launch_gemm_free_t(hipStream_t st, const GemmArgs& a) {
 inline int launch_gemm_free(hipStream_t st, const GemmArgs& a) {
   if ((a.x_frag && a.ldx % 16 != 0) || (a.y_frag && (a.ldy % 16 != 0 || (a.R && a.ldr % 16 != 0) || a.ldy < (a.N + 3) / 4 * 4)))
     return fail(GLAMR_E_INVALID, "fragment-major GEMM: ldx=%d / ldy=%d / ldr=%d must be multiples of 16", a.ldx, a.ldy, a.ldr);
-#ifndef GLAMR_FREE_GEMM_CFG
-#define GLAMR_FREE_GEMM_CFG 2, 1, 4      // development aid: column tiles per wave, k steps of operands ahead, waves per SIMD the allocation aims at
-#endif
   // few rows (the backward products of the taped infiller: 50 rows on an otherwise idle chip): ONE column tile per wave -- twice the waves, half the
   // chain of MFMAs in each (every output element is the same sum in the same order: bits unchanged)
   if (a.M <= 128 && !a.x_frag && !a.y_frag) return launch_gemm_free_t<1, 1, 4>(st, a);
-  return launch_gemm_free_t<GLAMR_FREE_GEMM_CFG>(st, a);
+  return launch_gemm_free_t<2, 1, 4>(st, a);      // column tiles per wave, k steps of operands ahead, waves per SIMD the allocation aims at
 }
 
 // Y[row] = LayerNorm(X[row] (+ R[row])) over 256 columns (add_layernorm_kernel's two-pass arithmetic), all three fragment-major; one wave per

@@ -14,15 +14,13 @@ namespace nn {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int GT_M = 64, GT_N = 64, GT_K = 32, GT_LD = 36;   // LDS row stride 36 floats: conflict-free ds_read_b128 over 16 rows
+constexpr int GT_N = 64, GT_K = 32, GT_LD = 36;   // LDS row stride 36 floats: conflict-free ds_read_b128 over 16 rows
 
 enum Act { ACT_NONE = 0, ACT_RELU = 1 };
 
 // Y[M,N] = act(X[M,K] W[N,K]^T + bias[N] + (rowbias ? rowbias[row / rows_per_group][N] : 0)) + (R ? R[M,N] : 0)
 // (rows_per_group < 0: a per-POSITION table instead, rowbias[row % -rows_per_group][N] -- the folded position codes of a window's tokens)
 //   X: ldx >= K (K multiple of 32, zero padded), W: [Npad][K] with Npad a multiple of 64 (zero rows), Y/R: ldy.
-// Tile 64x64 per 256-thread workgroup, each wave owns a 32x32 accumulator (v_mfma_f32_32x32x2_f32); both operands are staged
-// through LDS in 32-deep K chunks; lanes 0-31 / 32-63 consume the low / high 16 k of a chunk so every lane reads contiguous k.
 struct GemmArgs {
   const float* X; const float* W; const float* bias; const float* rowbias; const float* R; float* Y;
   int M, N, K, ldx, ldy, ldr, rows_per_group, ldrb, act;
@@ -31,82 +29,8 @@ struct GemmArgs {
   int x_frag = 0, y_frag = 0;             // gemm_free_kernel only (nn_free.hpp): X, resp. Y and R, in fragment-major order
 };
 
-__global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
-  // (two LDS buffers: one barrier per 32-deep chunk; the chunks' global loads run GT_PF chunks ahead in registers.  Round 3 loaded a chunk,
-  // waited, stored it and computed, with two barriers: a call with 64 rows -- the latent-optimisation mode makes 670 per iteration -- spent
-  // 8 memory latencies on K = 256: 14.8 us)
-  __shared__ __attribute__((aligned(16))) float sA[2][GT_M * GT_LD];
-  __shared__ __attribute__((aligned(16))) float sB[2][GT_N * GT_LD];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int col = lane & 31, half = lane >> 5;
-  const int m0 = blockIdx.y * GT_M, n0 = blockIdx.x * GT_N;
-  f32x16 acc = {0};
-  // staging map: 512 float4 per operand tile, two per thread
-  const int r0 = tid >> 3, c4 = (tid & 7) * 4;          // rows r0 and r0 + 32, k offset c4
-  constexpr int GT_PF = 4;
-  const int nchunks = a.K / GT_K;
-  f32x4 va[GT_PF][2], vb[GT_PF][2];
-  const float* xa[2];
-  const float* xb[2];
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const int r = r0 + q * 32;
-    xa[q] = a.X + (size_t)min(m0 + r, a.M - 1) * a.ldx + c4;
-    xb[q] = a.W + (size_t)(n0 + r) * a.K + c4;
-  }
-  auto fetch = [&](int c, int slot) {
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      va[slot][q] = *reinterpret_cast<const f32x4*>(xa[q] + c * GT_K);
-      vb[slot][q] = *reinterpret_cast<const f32x4*>(xb[q] + c * GT_K);
-    }
-  };
-#pragma unroll
-  for (int u = 0; u < GT_PF; ++u) if (u < nchunks) fetch(u, u);
-  for (int c0 = 0; c0 < nchunks; c0 += GT_PF) {
-#pragma unroll
-    for (int u = 0; u < GT_PF; ++u) {
-      const int c = c0 + u;
-      if (c >= nchunks) break;
-      float* bA = sA[c & 1];
-      float* bB = sB[c & 1];
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        *reinterpret_cast<f32x4*>(bA + (r0 + q * 32) * GT_LD + c4) = va[u][q];
-        *reinterpret_cast<f32x4*>(bB + (r0 + q * 32) * GT_LD + c4) = vb[u][q];
-      }
-      __syncthreads();
-      if (c + GT_PF < nchunks) fetch(c + GT_PF, u);
-      const float* pa = bA + (wm * 32 + col) * GT_LD + half * 16;
-      const float* pb = bB + (wn * 32 + col) * GT_LD + half * 16;
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) {
-        const f32x4 x = *reinterpret_cast<const f32x4*>(pa + s4 * 4);
-        const f32x4 w = *reinterpret_cast<const f32x4*>(pb + s4 * 4);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x[s], w[s], acc, 0, 0, 0);
-      }
-    }
-  }
-  // epilogue: lane owns column n0 + wn*32 + col, rows (r & 3) + 8 (r >> 2) + 4 half
-  const int n = n0 + wn * 32 + col;
-  if (n >= a.N) return;
-  const float b = a.bias ? a.bias[n] : 0.0f;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-    if (m >= a.M) continue;
-    float v = acc[r] + b;
-    if (a.rowbias) v += a.rowbias[(size_t)(a.rows_per_group > 0 ? m / a.rows_per_group : m % (-a.rows_per_group)) * a.ldrb + n];
-    if (a.act == ACT_RELU) v = fmaxf(v, 0.0f);
-    if (a.R) v += a.R[(size_t)m * a.ldr + n];
-    a.Y[(size_t)m * a.ldy + n] = v;
-  }
-}
-
-// The same contract for FEW rows (M < 2048, what launch_gemm does not hand to the split-fp16 kernel: a 50-frame window of one sequence -- a lone sequence's priors, the taped forward of the
-// latent-optimisation mode: ~330 such products per pass).  gemm_kernel's wave walks K with one accumulator of v_mfma_f32_32x32x2_f32: K / 2 dependent
+// The contract above in fp32 for FEW rows (M < SMALL_ROWS, what launch_gemm does not hand to the split-fp16 kernel: a 50-frame window of one sequence -- a lone sequence's priors, the taped forward of the
+// latent-optimisation mode: ~330 such products per pass).  A 64 x 64 tile whose wave walks K with one accumulator of v_mfma_f32_32x32x2_f32 (until round 5): K / 2 dependent
 // instructions of 64 cycles each, 3.4 us at K = 256 and 6.8 at 512, on 4 - 12 workgroups of a 256-CU chip.  Here a workgroup owns a 32 x 32 tile, each
 // wave a 16 x 16 accumulator walked with v_mfma_f32_16x16x4_f32 (K / 4 dependent instructions of ~40 cycles: 1.1 / 2.1 us) and four times as many
 // workgroups share the rows.  Products and sums stay fp32 (the split-fp16 kernels move a lone sequence's results out of the single-sequence parity bounds).
@@ -368,14 +292,14 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const float* X, cons
 
 // ---- fused row-block layers: activations stay on chip between the GEMMs of a block ------------------------------------------------
 // The priors' linear layers are K = 256 / 512 deep: as separate GEMMs each is an HBM round trip of its activations (52 MB in, 52-157 MB
-// out per 51 200 rows) and the matrix pipe idles 80 % of the time.  This kernel keeps a block of 64 rows in LDS through a whole
+// out per 51 200 rows) and the matrix pipe idles 80 % of the time.  This kernel keeps a block of 32 rows in LDS through a whole
 // sub-block of a transformer / MLP layer, with the full 256-wide output row in ONE workgroup so LayerNorm can follow in the epilogue:
 //   ONE layer :  Y = [LN]( act(X W2^T + b2) + R )                                   e.g. attention out-projection + residual + LayerNorm
 //   TWO layers:  H = relu(X W1^T + b1 [+ row bias]),  Y = [LN]( act(H W2^T + b2) + R )   feed-forward block (hidden 512 in two 256-column halves,
 //                                                                                     never leaving LDS), the MLPs of the trajectory predictor
 // X tile and hidden tile live in LDS as two fp16 planes (hi, lo; rows padded by 16 B: conflict-free ds_read_b128), i.e. directly as MFMA A
 // operands -- no per-k-step conversion; weights come from L2 in fragment order as in gemm_split_kernel, one k step ahead.  8 waves, each
-// owning 2 row tiles x 1 column tile of the 64 x 256 output (and of each hidden half).  LayerNorm arithmetic = add_layernorm_kernel.
+// owning the row tile x 1 column tile of the 32 x 256 output (and of each hidden half).  LayerNorm arithmetic = add_layernorm_kernel.
 struct RowsArgs {
   const float* X; int ldx, M, K1;                     // input rows [M][K1] (K1 multiple of 32, <= 256 with two layers, <= 512 with one)
   const unsigned short* W1s; size_t w1_plane;         // layer 1 weight planes (N = 512, K = K1), null for ONE layer
@@ -390,12 +314,13 @@ struct RowsArgs {
 // KS1 > 0: the k steps of the first GEMM phase are known at compile time (16 for the 256-wide transformer layers): every phase is then
 // straight-line code -- around a loop back edge the compiler cannot count the weight fragments in flight and waits for all of them at
 // the loop head, which defeats the three-steps-ahead prefetch.
-// RT: 32-row tiles per workgroup.  2 = 64 rows (135 KB of LDS with two layers: ONE workgroup per CU, its staging and epilogue overlap nobody's
-// MFMAs); 1 = 32 rows at half the LDS and <= 128 registers: TWO workgroups per CU, each wave then re-reads the weight fragments for half the
-// rows (twice the L2 traffic per row, still a fraction of its bandwidth).
-template <bool TWO, int KS1 = 0, int RT = 2>
-__global__ __launch_bounds__(512, RT == 1 ? 4 : 1) void rows_fused_kernel(RowsArgs a) {      // (second argument: waves per SIMD)
+// One 32-row tile per workgroup: half the LDS of 64 rows (135 KB with two layers: ONE workgroup per CU, its staging and epilogue overlap
+// nobody's MFMAs) and <= 128 registers: TWO workgroups per CU, each wave then re-reads the weight fragments for half the rows (twice the L2
+// traffic per row, still a fraction of its bandwidth).
+template <bool TWO, int KS1 = 0>
+__global__ __launch_bounds__(512, 4) void rows_fused_kernel(RowsArgs a) {      // (second argument: waves per SIMD)
   GLAMR_CRITICAL_PATH_PRIO();
+  constexpr int RT = 1;                                             // 32-row tiles per workgroup
   constexpr int RB = 32 * RT;                                       // rows per workgroup
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NJ = 1;                                             // 8 waves: one 32-column tile each (x 2 row tiles)
@@ -403,9 +328,9 @@ __global__ __launch_bounds__(512, RT == 1 ? 4 : 1) void rows_fused_kernel(RowsAr
   const int m0 = blockIdx.x * RB;
   const int K1 = a.K1, XS = (K1 + 8) * 2;                         // bytes per row of one X plane
   constexpr int HS = (256 + 8) * 2;                               // bytes per row of one hidden plane
-  unsigned char* sX = smem;                                       // [2][64][XS]
+  unsigned char* sX = smem;                                       // [2][RB][XS]
   unsigned char* sH = smem + 2 * RB * XS;                         // [2][RB][HS] (two layers only)
-  // the fp32 output rows [64][260] reuse the hidden planes (two layers) or the X planes (one layer, K1 = 256: 67.6 KB -> two workgroups per CU)
+  // the fp32 output rows [RB][260] reuse the hidden planes (two layers) or the X planes (one layer, K1 = 256: 67.6 KB -> two workgroups per CU)
   float* sOut = reinterpret_cast<float*>(TWO ? sH : sX);
   // ---- X tile -> planes ---------------------------------------------------------------------------------------------------------
   for (int f = tid; f < RB * (K1 / 4); f += 512) {
@@ -567,7 +492,8 @@ __global__ __launch_bounds__(512, RT == 1 ? 4 : 1) void rows_fused_kernel(RowsAr
   }
 }
 
-inline size_t rows_fused_lds(int K1, bool two, int rb = 64) {
+inline size_t rows_fused_lds(int K1, bool two) {
+  constexpr size_t rb = 32;
   const size_t x = (size_t)2 * rb * (K1 + 8) * 2, h = (size_t)2 * rb * (256 + 8) * 2;
   return two ? x + h : (x > (size_t)rb * 260 * 4 ? x : (size_t)rb * 260 * 4);
 }
@@ -733,10 +659,7 @@ struct QkvAttnArgs {
   float* O; int ldo;                             // [B][Lq][256]
 };
 
-#ifndef GLAMR_QKV_WAVES
-#define GLAMR_QKV_WAVES 1      // waves per SIMD the register allocation aims at (development knob)
-#endif
-__global__ __launch_bounds__(512, GLAMR_QKV_WAVES) void qkv_attention_kernel(QkvAttnArgs a) {
+__global__ __launch_bounds__(512, 1) void qkv_attention_kernel(QkvAttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int XS = (256 + 8) * 2;                               // bytes per row of one plane
   constexpr int KS = 16;                                          // k steps of the projections (K = 256)
@@ -812,7 +735,6 @@ __global__ __launch_bounds__(512, GLAMR_QKV_WAVES) void qkv_attention_kernel(Qkv
     }
   };
   f16x8 qh_[2][2], ql_[2][2], kh_[2][2], kl_[2][2];
-#ifndef GLAMR_QKV_NO_FUSE_QK
   if (self) {
     // self-attention: queries and keys are projections of the SAME rows -- one pass, the row fragments read once for four chains
     f32x16 acc[2][2] = {{(f32x16){0}, (f32x16){0}}, {(f32x16){0}, (f32x16){0}}};       // [q / k][tile]
@@ -855,9 +777,7 @@ __global__ __launch_bounds__(512, GLAMR_QKV_WAVES) void qkv_attention_kernel(Qkv
           if (m) split8(x, kh_[t][u], kl_[t][u]); else split8(x, qh_[t][u], ql_[t][u]);
         }
       }
-  } else
-#endif
-  {
+  } else {
     proj_t(sQ, two_q, a.Wq, a.wq_plane, a.q_nb0 + h, a.bq, 0.17677669529663687f, qh_, ql_);
     proj_t(sKV, two_k, a.Wkv, a.wkv_plane, a.k_nb0 + h, a.bkv, 1.0f, kh_, kl_);
   }
@@ -1135,22 +1055,22 @@ __global__ __launch_bounds__(512) void lstm_mfma_kernel(LstmArgs a, int n_seq) {
   }
 }
 
+// Below SMALL_ROWS rows every product runs on the fp32 kernels (gemm_small_kernel here, the fused row / attention kernels of nets.hip stay
+// off): a sequence alone and the same sequence inside a small batch then agree to the bit.  Small M is launch / latency bound either way.
+constexpr int SMALL_ROWS = 2048;
+
 inline int launch_gemm(hipStream_t st, const float* X, int ldx, const float* W, const float* bias, float* Y, int ldy, int M, int N, int K,
                        int act = ACT_NONE, const float* R = nullptr, int ldr = 0, const float* rowbias = nullptr, int rows_per_group = 1, int ldrb = 0,
                        const unsigned short* Ws = nullptr) {
   if (M <= 0) return GLAMR_OK;
   if (K % GT_K != 0 || ldx % 4 != 0) return fail(GLAMR_E_INVALID, "gemm: K=%d must be a multiple of %d and ldx=%d of 4", K, GT_K, ldx);
-  static const bool log_shapes = std::getenv("GLAMR_GEMM_LOG") != nullptr;      // development aid (tools/gemm_profile.py)
-  if (log_shapes) std::fprintf(stderr, "GEMM %d %d %d\n", M, N, K);
   GemmArgs a{X, W, bias, rowbias, R, Y, M, N, K, ldx, ldy, ldr, rows_per_group, ldrb, act};
   const int npad = (N + GT_N - 1) / GT_N * GT_N;
-  static const bool no_split = std::getenv("GLAMR_GEMM_FP32_MFMA") != nullptr;      // development aid: force the plain fp32 kernel
-  if (Ws && M >= 2048 && !no_split) {
-    // tall activations: the split-bf16 kernel (small M is launch / latency bound either way)
+  if (Ws && M >= SMALL_ROWS) {
+    // tall activations: the split-bf16 kernel
     a.Ws = Ws;
     a.ws_plane = (size_t)npad * K;
-    const bool narrow_only = std::getenv("GLAMR_GEMM_NARROW") != nullptr;      // development aid: 128x64 tiles only (116 registers)
-    if (!narrow_only && npad % 128 == 0 && (size_t)(M / 128) * (npad / 128) >= 512)
+    if (npad % 128 == 0 && (size_t)(M / 128) * (npad / 128) >= 512)
       hipLaunchKernelGGL((gemm_split_kernel<2>), dim3(npad / 128, ((M + 127) / 128 + 7) / 8 * 8), dim3(256), 0, st, a);
     else
       hipLaunchKernelGGL((gemm_split_kernel<1>), dim3(npad / 64, ((M + 127) / 128 + 7) / 8 * 8), dim3(256), 0, st, a);
@@ -1158,12 +1078,7 @@ inline int launch_gemm(hipStream_t st, const float* X, int ldx, const float* W, 
   }
   // (measured and dropped, round 4: the K loop of a tile over two groups of four waves for grids of a handful of workgroups -- 13.3 against 12.4 us
   // per call at M = 50: these calls are launch + latency, not the chain of fp32 MFMAs)
-  static const bool no_small = [] { const char* e = std::getenv("GLAMR_GEMM_SMALL16"); return e && e[0] == '0'; }();      // development aid: gemm_kernel for few rows as well
-  if (!no_small) {      // (every product that is not on the split-fp16 kernels: a sequence alone and the same sequence inside a small batch then agree to the bit)
-    hipLaunchKernelGGL(gemm_small_kernel, dim3((N + 31) / 32, (M + 31) / 32), dim3(256), 0, st, a);
-    return GLAMR_OK;
-  }
-  hipLaunchKernelGGL(gemm_kernel, dim3((N + GT_N - 1) / GT_N, (M + GT_M - 1) / GT_M), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(gemm_small_kernel, dim3((N + 31) / 32, (M + 31) / 32), dim3(256), 0, st, a);
   return GLAMR_OK;
 }
 
@@ -1175,21 +1090,14 @@ inline int launch_rows(hipStream_t st, const float* X, int ldx, int M, int K1, c
   if (K1 % 32 != 0 || ldx % 4 != 0 || ldy % 4 != 0 || (W1s && (K1 > 256 || K2 != 512)) || (!W1s && (K1 > 256 || K2 != K1)))
     return fail(GLAMR_E_INVALID, "fused rows: unsupported shape K1=%d K2=%d", K1, K2);
   RowsArgs a{X, ldx, M, K1, W1s, w1_plane, b1, rowbias, rpg, ldrb, W2s, w2_plane, K2, b2, act2, R, ldr, gamma, beta, Y, ldy};
-  // 32-row blocks: two workgroups per CU (measured on 1024 x 300 frames, both priors: 20.6 ms against 21.7 with 64-row blocks);
-  // GLAMR_ROWS_RT=2 selects the 64-row instances (A/B runs)
-  static const int rt_env = std::getenv("GLAMR_ROWS_RT") ? std::atoi(std::getenv("GLAMR_ROWS_RT")) : 0;
-  static const int rt_one = std::getenv("GLAMR_ROWS_RT_ONE") ? std::atoi(std::getenv("GLAMR_ROWS_RT_ONE")) : 0;      // (one-layer blocks only)
-  const int rt_sel = (!W1s && (rt_one == 1 || rt_one == 2)) ? rt_one : rt_env;
-  const int rt = rt_sel == 1 || rt_sel == 2 ? rt_sel : 1;
-  const int rb = 32 * rt;
+  // 32-row blocks: two workgroups per CU (measured on 1024 x 300 frames, both priors: 20.6 ms against 21.7 with 64-row blocks)
+  constexpr int rb = 32;
   if (rowbias && (rpg < rb || !W1s)) return fail(GLAMR_E_INVALID, "fused rows: a row bias needs two layers and groups of at least %d rows (got %d)", rb, rpg);
-  const size_t lds = rows_fused_lds(K1, W1s != nullptr, rb);
+  const size_t lds = rows_fused_lds(K1, W1s != nullptr);
   static bool attr_done = false;
   if (!attr_done) {
     const void* kerns[] = {reinterpret_cast<const void*>(rows_fused_kernel<true>), reinterpret_cast<const void*>(rows_fused_kernel<false>),
-                           reinterpret_cast<const void*>(rows_fused_kernel<true, 16>), reinterpret_cast<const void*>(rows_fused_kernel<false, 16>),
-                           reinterpret_cast<const void*>(rows_fused_kernel<true, 0, 1>), reinterpret_cast<const void*>(rows_fused_kernel<false, 0, 1>),
-                           reinterpret_cast<const void*>(rows_fused_kernel<true, 16, 1>), reinterpret_cast<const void*>(rows_fused_kernel<false, 16, 1>)};
+                           reinterpret_cast<const void*>(rows_fused_kernel<true, 16>), reinterpret_cast<const void*>(rows_fused_kernel<false, 16>)};
     for (const void* k : kerns)
       if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024) != hipSuccess) return fail(GLAMR_E_HIP, "hipFuncSetAttribute(rows_fused_kernel) failed");
     attr_done = true;
@@ -1197,13 +1105,8 @@ inline int launch_rows(hipStream_t st, const float* X, int ldx, int M, int K1, c
   // K1 = 256 (every transformer block): the instances whose phases are straight-line code
   const bool k256 = K1 == 256;
   const dim3 grid((M + rb - 1) / rb), block(512);
-  if (rt == 1) {
-    if (W1s) { if (k256) hipLaunchKernelGGL((rows_fused_kernel<true, 16, 1>), grid, block, lds, st, a); else hipLaunchKernelGGL((rows_fused_kernel<true, 0, 1>), grid, block, lds, st, a); }
-    else { if (k256) hipLaunchKernelGGL((rows_fused_kernel<false, 16, 1>), grid, block, lds, st, a); else hipLaunchKernelGGL((rows_fused_kernel<false, 0, 1>), grid, block, lds, st, a); }
-  } else {
-    if (W1s) { if (k256) hipLaunchKernelGGL((rows_fused_kernel<true, 16>), grid, block, lds, st, a); else hipLaunchKernelGGL(rows_fused_kernel<true>, grid, block, lds, st, a); }
-    else { if (k256) hipLaunchKernelGGL((rows_fused_kernel<false, 16>), grid, block, lds, st, a); else hipLaunchKernelGGL(rows_fused_kernel<false>, grid, block, lds, st, a); }
-  }
+  if (W1s) { if (k256) hipLaunchKernelGGL((rows_fused_kernel<true, 16>), grid, block, lds, st, a); else hipLaunchKernelGGL(rows_fused_kernel<true>, grid, block, lds, st, a); }
+  else { if (k256) hipLaunchKernelGGL((rows_fused_kernel<false, 16>), grid, block, lds, st, a); else hipLaunchKernelGGL(rows_fused_kernel<false>, grid, block, lds, st, a); }
   return GLAMR_OK;
 }
 

@@ -316,15 +316,7 @@ struct LbsArgs {
   const float* root_trans;  // (B,3)
   const float* root_scale;  // (B) or null
   int skip_picks;           // the joints pass already captured the picked vertices
-#ifdef GLAMR_SMPL_EXPERIMENT
-  int exp;                  // development builds: ablation switches (tools/smpl_ablate.py)
-#endif
 };
-#ifdef GLAMR_SMPL_EXPERIMENT
-#define GLAMR_SMPL_EXP(a, bit) (((a).exp & (bit)) != 0)
-#else
-#define GLAMR_SMPL_EXP(a, bit) false
-#endif
 
 __device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
@@ -416,7 +408,7 @@ __global__ __launch_bounds__(F16 ? 512 : 256) void smpl_lbs_kernel(LbsArgs a) {
       // lane half h supplies k = 112 h + 8 m .. + 7 to k step m, on both operands alike.  The feature planes are fragment-major: the
       // fetch of (plane, step) is ONE contiguous 1 KB read per wave, requested PF steps before its MFMAs
       const unsigned short* myH = reinterpret_cast<const unsigned short*>(sDirs) + (size_t)col * KSH + half * KH;
-      const uint4* fq = reinterpret_cast<const uint4*>(a.feat_h) + (GLAMR_SMPL_EXP(a, 8) ? (size_t)wave : (size_t)ft) * (FEAT_TILE_H / 8) + lane;
+      const uint4* fq = reinterpret_cast<const uint4*>(a.feat_h) + (size_t)ft * (FEAT_TILE_H / 8) + lane;
       constexpr int PF = 3, RING = PF + 1;
       uint4 qh[RING], ql[RING];
       uint4 ah[2][3], al[2][3];          // direction fragments (LDS), one k step ahead as well
@@ -485,7 +477,7 @@ __global__ __launch_bounds__(F16 ? 512 : 256) void smpl_lbs_kernel(LbsArgs a) {
       // (r, m, pair of c) of four fetches and six MFMAs each; the fetches of a phase are requested before the MFMAs of the one before it
       // (a ring of three sets, two phases ahead, costs 16 more registers: the epilogue then spills addresses, and a scratch reload waits on
       // vmcnt(0) -- on every vertex store still in flight; the ablations say the operand fetches are 0.2 of 1.5 ms, the epilogue 0.75)
-      const uint4* aq = reinterpret_cast<const uint4*>(a.askin_h) + (GLAMR_SMPL_EXP(a, 4) ? (size_t)wave : (size_t)ft) * (ASK_TILE_H / 8) + lane;
+      const uint4* aq = reinterpret_cast<const uint4*>(a.askin_h) + (size_t)ft * (ASK_TILE_H / 8) + lane;
       uint4 qa[2][2][2];      // [ring][c of the pair][plane]
       auto fetch = [&](int ph, int buf) {
         const int r = ph >> 2, m = (ph >> 1) & 1, cp = ph & 1;
@@ -570,9 +562,9 @@ __global__ __launch_bounds__(F16 ? 512 : 256) void smpl_lbs_kernel(LbsArgs a) {
     // vertex write-out through an LDS transpose: [frame][vertex row][xyz] so each frame's 96 floats are contiguous.  A lane's 16 accumulator
     // rows are four runs of four consecutive vertices = 12 consecutive floats each: three ds_write_b128 per run; the rows leave as 16-byte
     // pieces, two frame rows per store instruction
-    if (a.verts && !GLAMR_SMPL_EXP(a, 2)) {
+    if (a.verts) {
       float* so = sOut + (size_t)wave * OF * OUT_STRIDE;
-      const int nvalid = GLAMR_SMPL_EXP(a, 1) ? 0 : min(TILE_V, a.V - v0) * 3;
+      const int nvalid = min(TILE_V, a.V - v0) * 3;
       const bool wide = (a.V & 1) == 0;
 #pragma unroll
       for (int pass = 0; pass < TILE_F / OF; ++pass) {
@@ -1279,9 +1271,9 @@ extern "C" int glamr_smpl_forward(glamr_smpl* h, int B, const float* pose, const
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   SmplWs w = smpl_ws_layout(h, B, static_cast<char*>(workspace));
   const bool orig = (flags & GLAMR_SMPL_ORIG_JOINTS) != 0;
-  // blend shapes and skinning transforms on the fp16 matrix cores (two-plane operands: fp32-grade products); GLAMR_SMPL_FP32_BLEND=1
-  // selects the fp32-MFMA instances (and then the planes of the feature rows / joint transforms are not written)
-  const bool planes = std::getenv("GLAMR_SMPL_FP32_BLEND") == nullptr && h->full.dirs_h != nullptr && (h->joints.n_tiles == 0 || h->joints.dirs_h != nullptr);
+  // blend shapes and skinning transforms on the fp16 matrix cores (two-plane operands: fp32-grade products) when the handle holds the
+  // planes of its directions; otherwise the fp32-MFMA instances (and then the planes of the feature rows / joint transforms are not written)
+  const bool planes = h->full.dirs_h != nullptr && (h->joints.n_tiles == 0 || h->joints.dirs_h != nullptr);
   // (rows [B, Bpad) of the operand arrays, read by the padded MFMA tiles, are written as zeros by the prep kernel)
   // (the fp16-plane instances read nothing but the planes: the fp32 rows are only written for the fp32-MFMA instances)
   PrepArgs pa{B, w.Bpad, h->num_betas, h->n_levels, 1, pose, (flags & GLAMR_SMPL_BODY_POSE_ONLY) ? 1 : 0, betas, h->j_template, h->j_shapedirs, h->parents, h->level, planes ? nullptr : w.feat,
@@ -1296,11 +1288,7 @@ extern "C" int glamr_smpl_forward(glamr_smpl* h, int B, const float* pose, const
     LbsArgs la{B, h->V, ts.n_tiles, n_ftiles, ne, h->n_picked, ts.dirs_tiled, ts.w_tiled, ts.jx_used,
                ts.tile_pick_start, ts.tile_pick_ids, ts.pick_row, w.feat, ts.dirs_h, reinterpret_cast<const unsigned short*>(w.feat_h),
                reinterpret_cast<const unsigned short*>(w.askin_h), w.askin, vout, w.picked, w.partial, w.Bpad,
-               pivot, root_trans, root_scale, skip_picks ? 1 : 0
-#ifdef GLAMR_SMPL_EXPERIMENT
-               , std::getenv("GLAMR_SMPL_EXP") ? std::atoi(std::getenv("GLAMR_SMPL_EXP")) : 0
-#endif
-    };
+               pivot, root_trans, root_scale, skip_picks ? 1 : 0};
     const size_t lds = dirs_bytes + (vout ? (size_t)nw * (f16 ? TILE_F / 2 : TILE_F) * OUT_STRIDE * sizeof(float) : 0);
     // frame tiles are split over gridDim.y so that a launch has ~4 workgroups per CU even with few vertex tiles; every workgroup
     // re-stages its 87 KB direction tile, so a chunk keeps >= 8 frame tiles per wave

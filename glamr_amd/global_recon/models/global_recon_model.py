@@ -730,44 +730,30 @@ class GlobalReconOptimizer:
                 self._capture_split()                                   # capture_resident under a gate: the graph is cut here
             elif gate is not None and not torch.cuda.is_current_stream_capturing():
                 gate.after(torch.cuda.current_stream(dev))
-        # the next batch may start when this batch's priors are done -- or (GLAMR_GATE_AFTER=infiller) already when its infiller is
-        # (development aid GLAMR_GATE_AFTER: 'infiller' / 'priors' (default) / 'scene' / 'skin' / 'forward' -- later = the rest of this batch's
-        # preparation runs without the next batch's first kernels beside it, but that batch starts later: profiles/r05_pipeline_experiments.log)
-        gate_at = os.environ.get('GLAMR_GATE_AFTER', 'priors') if gate is not None else 'priors'
+        # the next batch may start when this batch's priors are done (opening the gate later lets the rest of this batch's preparation run
+        # without the next batch's first kernels beside it, but that batch starts later: profiles/r05_pipeline_experiments.log)
         # Under a gate the SKINNING runs between the infiller and the trajectory predictor, i.e. before the gate opens: everything it needs (the
         # infilled poses in video-frame rows, glamr_init_scatter_pose) is known by then, and it runs alone (1.5 ms) instead of beside the next batch's
         # first kernels (2.4 ms): 34.7 against 35.4 ms per step (profiles/r06_pipeline_corruption.log).  (Round 5 moved it there to dodge the
         # corruption of its results beside the other stream's attention kernels; with that fixed at its root the order is kept for its speed.)
-        # GLAMR_SKIN_AFTER_PRIORS=1 restores the old order (development aid).
-        skin_early = gate is not None and os.environ.get('GLAMR_SKIN_AFTER_PRIORS') != '1' and gate_at in ('priors', 'infiller', 'skin') \
-            and hasattr(self.mt_model, 'handle')
+        skin_early = gate is not None and hasattr(self.mt_model, 'handle')
 
         def skin():
             # root-relative joints of every frame, cached for the whole optimisation
             packed.t['j_local'] = self.smpl.root_relative_joints(pa_t['smpl_pose'].view(-1, 69), pa_t['smpl_beta'].view(-1, 10)).view(n_slots, T, 26, 3)
 
-        def after_infiller(out_inf):
-            if gate_at == 'infiller':
-                open_gate()
-            if skin_early:
-                _lib.check(L.glamr_init_scatter_pose(ctypes.byref(sb), ctypes.byref(pa), _lib.ptr(out_inf['pose']), st))
-                skin()
-                if gate_at == 'skin':
-                    open_gate()                                         # (the next batch's infiller beside this batch's trajectory predictor)
+        def skin_after_infiller(out_inf):
+            _lib.check(L.glamr_init_scatter_pose(ctypes.byref(sb), ctypes.byref(pa), _lib.ptr(out_inf['pose']), st))
+            skin()
         out = self.mt_model.infer_padded(pa_t['nets_pose'], pa_t['nets_vis'], rin.lens, meps, teps, buffers=rs, coschedule=gate is not None,
-                                         between=after_infiller if (skin_early or gate_at == 'infiller') else None)
-        if gate_at == 'priors':
-            open_gate()
+                                         between=skin_after_infiller if skin_early else None)
+        open_gate()
         packed.latents = (meps, teps)                                  # the draws this batch was initialised with (parameters in latent-optimisation mode)
         # (flag_traj_from_cam :237,325-351: the base pose of the frames outside a person's existence range read off the initial camera)
         _lib.check(L.glamr_init_scenes_ex(ctypes.byref(sb), ctypes.byref(pa), _lib.ptr(out['pose']), _lib.ptr(out['local_traj']), _lib.ptr(out['trans']),
                                           _lib.ptr(out['orient']), (1 if self.flag_traj_from_cam else 0) | (2 if skin_early else 0), _lib.ptr(ws), st))
-        if gate_at == 'scene':
-            open_gate()
         if not skin_early:
             skin()
-        if gate_at == 'skin' and not skin_early:
-            open_gate()
         # with flag_init_cam_all_frames this pass is only there for the world poses the cameras are initialised from; whoever needs the 'init'
         # outputs gets them from the second pass (init_forward), or from the first stage's last evaluation
         self._run(packed, self._forward_only_desc(poses_only=self.flag_init_cam_all_frames or not init_forward))
@@ -778,8 +764,6 @@ class GlobalReconOptimizer:
             # values); a caller that runs the schedule right away overwrites every one of them with the first stage's last evaluation
             if init_forward:
                 self._run(packed, self._forward_only_desc())
-        if gate_at == 'forward':
-            open_gate()
         packed.person_arrays = pa_t
         packed.exists = rin.exists
         packed.keepalive = (rin, ws, out)
@@ -1314,10 +1298,10 @@ class GlobalReconOptimizer:
         # The interpreter's cyclic collector: a full collection walks every container object alive -- with torch imported, 30-45 ms -- and the
         # ~10 000 containers a batch of output dictionaries is made of trigger one every 5-6 batches (measured: every fifth yield 85-110 ms late,
         # tools/stream_yield_probe.py).  While the stream runs, everything alive at its start sits in the permanent generation (gc.freeze):
-        # collections still run, over the objects created since.  GLAMR_STREAM_GC_FREEZE=0 leaves the collector alone.
+        # collections still run, over the objects created since.
         import gc
         # (a caller that keeps a frozen set of its own -- gc.get_freeze_count() > 0 -- manages the collector itself: gc.unfreeze() would release ITS set too)
-        frozen = gc.isenabled() and gc.get_freeze_count() == 0 and os.environ.get('GLAMR_STREAM_GC_FREEZE', '1') != '0'
+        frozen = gc.isenabled() and gc.get_freeze_count() == 0
         if frozen:
             # (no gc.collect() first: a full collection at this point walks every object alive -- 67 ms with torch imported, tools/stream_profile.py,
             # at the head of every stream, before its first batch is even staged; whatever garbage is frozen along is collected after gc.unfreeze())

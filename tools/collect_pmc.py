@@ -91,10 +91,29 @@ def calib():
     torch.cuda.synchronize()
 
 
+def priors_call():
+    """The workload of priors(): both networks on 1024 x 300 frames, twice (the first call builds the library's graph)."""
+    sys.path.insert(0, ROOT)
+    import torch
+    import bench
+    from glamr_amd.models.priors import num_windows
+    dev = torch.device('cuda:0')
+    m = bench.build_model(bench.ensure_assets(), dev)
+    g = torch.Generator().manual_seed(0)
+    n, T = 1024, 300
+    pose = (torch.randn(n, T, 69, generator=g) * 0.2).to(dev)
+    vis = torch.ones(n, T, device=dev)
+    vis[:, 100:160] = 0
+    meps, teps = torch.randn(n, num_windows(T), 128, generator=g).to(dev), torch.randn(n, 128, generator=g).to(dev)
+    for _ in range(2):
+        m.mt_model.infer_padded(pose, vis, [T] * n, meps, teps)
+    torch.cuda.synchronize()
+
+
 def priors():
-    """Matrix-pipe utilisation of the priors' kernels (one call of both networks on 1024 x 300 frames, tools/priors_ab.py)."""
+    """Matrix-pipe utilisation of the priors' kernels (priors_call)."""
     os.makedirs(OUT, exist_ok=True)
-    cmd = 'python %s/tools/priors_ab.py' % ROOT
+    cmd = 'python %s priors_call' % os.path.abspath(__file__)
     agg = {}
     for tag, ctrs in (('mfma', ['MfmaUtil']), ('mops', ['SQ_INSTS_VALU_MFMA_MOPS_F16', 'SQ_INSTS_VALU_MFMA_MOPS_F32']), ('busy', ['SQ_BUSY_CU_CYCLES', 'SQ_WAVE_CYCLES', 'SQ_WAIT_ANY'])):
         for r in run_pass('pri_' + tag, ctrs, cmd):
@@ -115,5 +134,7 @@ if __name__ == '__main__':
         calib()
     elif len(sys.argv) > 1 and sys.argv[1] == 'priors':
         priors()
+    elif len(sys.argv) > 1 and sys.argv[1] == 'priors_call':
+        priors_call()
     else:
         main()

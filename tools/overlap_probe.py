@@ -1,5 +1,5 @@
-"""Development probe: does a smaller optimiser arena (LDS left to co-resident kernels) + narrow GEMM tiles (116 registers) let the
-prior networks of one batch run UNDER the optimiser stage of the previous one?  Sweeps the two runtime knobs in one process."""
+"""Development probe: does a smaller optimiser arena (LDS left to co-resident kernels) let the prior networks of one batch run UNDER the
+optimiser stage of the previous one?  Sweeps the arena size and the number of streams in one process."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -42,21 +42,12 @@ def run(nstreams, steps=6, warmup=2):
     return ms, [round(model.launch_ms(ws), 1) for ws in p.stage_ws]
 
 
-CONFIGS = [(150, 0, 1), (150, 0, 2), (120, 0, 2), (120, 1, 2), (120, 1, 1), (96, 1, 2), (96, 1, 3), (64, 1, 2), (64, 0, 2), (64, 1, 1)]
+CONFIGS = [(150, 1), (150, 2), (120, 2), (120, 1), (96, 2), (96, 3), (64, 2), (64, 1)]
 if os.environ.get('GLAMR_PROBE_CONFIGS'):
     CONFIGS = [tuple(int(v) for v in c.split(',')) for c in os.environ['GLAMR_PROBE_CONFIGS'].split(';')]
-for cfg in CONFIGS:
-    lds, narrow, ns = cfg[:3]
-    if len(cfg) > 3:
-        os.environ['GLAMR_GRECON_THREADS_RT'] = str(cfg[3])
-    else:
-        os.environ.pop('GLAMR_GRECON_THREADS_RT', None)
+for lds, ns in CONFIGS:
     os.environ.pop('GLAMR_GRECON_LDS_KB_RT', None)          # 0 = the launcher's own policy
     if lds:
         os.environ['GLAMR_GRECON_LDS_KB_RT'] = str(lds)
-    if narrow:
-        os.environ['GLAMR_GEMM_NARROW'] = '1'
-    else:
-        os.environ.pop('GLAMR_GEMM_NARROW', None)
     ms, k = run(ns)
-    print('threads %s lds %3d KB narrow %d streams %d : %.1f ms/step  %.0f seq/s  last stage launches %s' % (cfg[3] if len(cfg) > 3 else 'auto', lds, narrow, ns, ms, B / ms * 1e3, k), flush=True)
+    print('lds %3d KB streams %d : %.1f ms/step  %.0f seq/s  last stage launches %s' % (lds, ns, ms, B / ms * 1e3, k), flush=True)

@@ -3,8 +3,8 @@ profiles/r06_pipeline_corruption.log; tests/test_pipeline_soak_gpu.py is its per
 Two step graphs (one per stream) are replayed as a PAIR, the device is synchronised, and every array of both is compared bit for bit with a plain
 step of the same seed; the seeds alternate between iterations so that a value left over from the previous replay is a wrong one.
 To see the corruption again build a library WITH packed-fp32 instructions: GLAMR_VARIANT_PACKED=" " tools/build_variant_files.sh packed
-"smpl.hip init.hip nets.hip eval.hip"; GLAMR_LIB_PATH=tools/_lib_packed.so GLAMR_SKIN_AFTER_PRIORS=1 python tools/race_probe.py
-knobs: GLAMR_GATE_PREP=late, GLAMR_SKIN_AFTER_PRIORS=1, GLAMR_PROBE_TWO_INPUTS=1, GLAMR_PROBE_LATENTS=1, GLAMR_PROBE_SNAPSHOT=1 (the skinning's workspace
+"smpl.hip init.hip nets.hip eval.hip"; GLAMR_LIB_PATH=tools/_lib_packed.so python tools/race_probe.py
+knobs: GLAMR_GATE_PREP=late, GLAMR_PROBE_TWO_INPUTS=1, GLAMR_PROBE_LATENTS=1, GLAMR_PROBE_SNAPSHOT=1 (the skinning's workspace
 copied inside the graphs), GLAMR_PROBE_HOST_WAIT=1, GLAMR_PROBE_SPIN_US=n, GLAMR_PROBE_B=graph|nets|mm|add|sleep|none (what the second stream runs)
 usage: python tools/race_probe.py [n_sequences] [iterations]"""
 import os, sys
@@ -106,7 +106,7 @@ for gi, r in enumerate(rins):
         ref_snaps[(gi, seed)] = {k: v.clone() for k, v in snap_latest.items()}
         refs[(gi, seed)] = ({k: ref.t[k].clone() for k in keys}, {k: v.clone() for k, v in ref.person_arrays.items() if torch.is_tensor(v)}, [x.clone() for x in ref.latents])
 model.pipeline_gate.last = None
-print('gate cut: %s, skinning %s, %d sequences' % (os.environ.get('GLAMR_GATE_PREP', 'late'), 'after the priors (old order)' if os.environ.get('GLAMR_SKIN_AFTER_PRIORS') == '1' else 'before the predictor', B))
+print('gate cut: %s, %d sequences' % (os.environ.get('GLAMR_GATE_PREP', 'late'), B))
 
 
 def compare(g, ref):
