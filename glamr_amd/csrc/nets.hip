@@ -442,15 +442,17 @@ int mlp2(hipStream_t st, const Lin& L1, const Lin& L2, const LN* n, const float*
 // the fp32 GEMM of round 5 walked K with v_mfma_f32_32x32x2_f32 on ONE accumulator per wave -- a chain of K / 2 dependent 64-cycle instructions, 3.4 us at
 // K = 256 and 6.8 at 512 inside a 12 us kernel.  The one-wave split-fp16 kernel of nn_free.hpp (three v_mfma_f32_32x32x16_f16 per 16 k on two
 // column tiles, operands one step ahead, no LDS, no barrier) does the same product in 1.3 / 2.6 us of matrix time, on row-major rows as they are.
-// It takes the BACKWARD products (lin_bwd: gradient rows times transposed weights; 12.8 -> 11.2 ms per iteration of the mode).  The forward
-// products of few rows stay on the fp32 instruction: with them on the split kernel as well the mode runs at 10.5 ms, but the first gradient of
+// It takes the BACKWARD products (lin_bwd: gradient rows times transposed weights; 12.8 -> 11.2 ms per iteration of the mode) at every number of
+// rows, as the RS instances of gemm_free_kernel: no range analysis bounds a gradient (its size follows the loss weights, the frame count and the data), so
+// each row is scaled by a power of two taken from its own largest entry before the fp16 split and scaled back after the product (exact both
+// ways).  Unscaled (and on the LDS split kernel launch_gemm picks from SMALL_ROWS rows on), an upstream gradient 2^14 times the fixtures'
+// became inf and then NaN, and small ones fell into fp16's subnormals; the result depended on the gradient's magnitude
+// (tests/test_nets_vjp_gpu.py).  Chosen over sending the backward to the fp32 kernel, which costs the 1.6 ms above: the row scaling costs
+// one extra read of the row before the product: 8.58 -> 9.18 ms per iteration of the mode (tools/latent_time.py, parent and this build
+// alternated on one box).  The forward products of few rows stay on the fp32 instruction: with them on the split kernel as well the mode runs at 10.5 ms, but the first gradient of
 // the motion latent moves by 3.8e-6 of its largest entry and, eight Adam steps later, the latent of one of the three reference fixtures is 9.5e-4
 // away instead of 1.4e-6 (Adam's first steps are sign-like: an entry whose gradient is ~0 takes a full step the other way) -- outside the 1e-4
 // tests/test_latent_gpu.py holds it to.
-inline bool small_rows_split(const Lin& L, int M, int ldx, int ldy, int ldr, int ldrb, bool bwd) {
-  return bwd && !tl_fp32 && L.Ws && M > 0 && M < SMALL_ROWS && L.K % 32 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldr % 4 == 0 && ldrb % 4 == 0;
-}
-
 int lin(hipStream_t st, const Lin& L, const float* X, int ldx, float* Y, int ldy, int M, int act = ACT_NONE, const float* R = nullptr, int ldr = 0,
         const float* rowbias = nullptr, int rpg = 1, int ldrb = 0, int xl = -1, int yl = -1, bool bwd = false) {
   // xl / yl (free mode only): layout of X, resp. Y and R -- 1 fragment-major (the default there), 0 row-major (what an LDS kernel or a small
@@ -464,11 +466,13 @@ int lin(hipStream_t st, const Lin& L, const float* X, int ldx, float* Y, int ldy
     a.y_frag = yl != 0;
     return launch_gemm_free(st, a);
   }
-  if (small_rows_split(L, M, ldx, ldy, R ? ldr : 4, rowbias ? ldrb : 4, bwd)) {
+  if (bwd && !tl_fp32 && L.Ws && M > 0) {
+    if (L.K % 32 != 0 || ldx % 4 != 0 || ldy % 4 != 0 || (R && ldr % 4 != 0) || rowbias)
+      return fail(GLAMR_E_INVALID, "backward gemm: K=%d must be a multiple of 32, ldx=%d / ldy=%d / ldr=%d of 4, no row bias", L.K, ldx, ldy, ldr);
     GemmArgs a{X, L.W, L.b, rowbias, R, Y, M, L.N, L.K, ldx, ldy, ldr, rpg, ldrb, act};
     a.Ws = L.Ws;
     a.ws_plane = (size_t)((L.N + 63) / 64 * 64) * L.K;
-    return launch_gemm_free(st, a);                       // (row-major X, Y and R: x_frag = y_frag = 0)
+    return launch_gemm_free_bwd(st, a);                   // (row-major X, Y and R: x_frag = y_frag = 0)
   }
   return launch_gemm(st, X, ldx, L.W, L.b, Y, ldy, M, L.N, L.K, act, R, ldr, rowbias, rpg, ldrb, L.Ws);
 }

@@ -287,7 +287,7 @@ int lin_bwd(const TapeCtx& c, const Lin& L, float* dY, int ldy, const float* Y, 
   const Lin* T = transposed(c.h, L);
   if (!T) return fail(GLAMR_E_HIP, "could not build the transposed weights of a layer");
   if (T->K > ldy) return fail(GLAMR_E_INVALID, "lin_bwd: gradient rows of %d floats, %d needed", ldy, T->K);
-  return lin(c.st, *T, dY, ldy, dX, ldx, M, ACT_NONE, dX, ldx, nullptr, 1, 0, -1, -1, true);      // accumulates through the residual input (few rows: the one-wave split-fp16 kernel)
+  return lin(c.st, *T, dY, ldy, dX, ldx, M, ACT_NONE, dX, ldx, nullptr, 1, 0, -1, -1, true);      // accumulates through the residual input (the row-scaled one-wave split-fp16 kernel)
 }
 int ln_bwd(const TapeCtx& c, const LN& n, const float* dY, const float* X, const float* R, float* dX, float* dR, int rows) {
   hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, c.st, dY, X, R, n.g, dX, dR, rows);

@@ -46,7 +46,12 @@ __device__ __forceinline__ float lane_xor32(float x) {
   return __uint_as_float((threadIdx.x & 32) ? r[0] : r[1]);
 }
 
-template <int KS, int C, int PD, int MAXW>
+// RS (the backward products: gradient rows times transposed weights, whose size no range analysis bounds): every row is scaled by a power of
+// two 2^-e before the fp16 split, e = ilogb(largest |entry| of the row) - 14 (0 for an all-zero or non-finite row), so that its largest entry
+// lies in [2^14, 2^15) -- far from fp16's overflow and with the low plane of even 2^-24-relative entries above the subnormals -- and the
+// accumulator is scaled back by 2^e before the epilogue.  Both steps are exact: the result does not depend on the rows' magnitude, and
+// scaling a row by 2^k scales its output row by 2^k bit for bit.  Without RS the kernel is the forward one unchanged.
+template <int KS, int C, int PD, int MAXW, bool RS = false>
 __global__ __launch_bounds__(64, MAXW) void gemm_free_kernel(GemmArgs a) {
   const int lane = threadIdx.x, c = lane & 31, kg = lane >> 5;
   const int ncb = (a.N + 32 * C - 1) / (32 * C);
@@ -59,6 +64,18 @@ __global__ __launch_bounds__(64, MAXW) void gemm_free_kernel(GemmArgs a) {
   // per k step: 8 consecutive floats per lane; fragment-major: 2 KB per step, row-major: 64 B of each of the 32 rows
   const float* xp = a.x_frag ? a.X + ((size_t)rb * (a.ldx >> 4) * 64 + lane) * 8 : a.X + (size_t)min(row, a.M - 1) * a.ldx + 8 * kg;
   const int xstep = a.x_frag ? 512 : 16;
+  int e = 0;
+  // RS: the row's largest magnitude -- this lane's half of its K entries, then the other half from lane ^ 32 (same row); called once the first
+  // operand fetch is issued
+  auto row_exponent = [&]() {
+    float m = 0.f;
+    for (int ks = 0; ks < ksteps; ++ks) {
+      const f32x4 u = *reinterpret_cast<const f32x4*>(xp + (size_t)ks * xstep), w = *reinterpret_cast<const f32x4*>(xp + (size_t)ks * xstep + 4);
+      m = fmaxf(m, fmaxf(fmaxf(fmaxf(fabsf(u[0]), fabsf(u[1])), fmaxf(fabsf(u[2]), fabsf(u[3]))), fmaxf(fmaxf(fabsf(w[0]), fabsf(w[1])), fmaxf(fabsf(w[2]), fabsf(w[3])))));
+    }
+    m = fmaxf(m, lane_xor32(m));
+    e = (m > 0.f && m < INFINITY) ? ilogbf(m) - 14 : 0;
+  };
   const int ntile = (a.N + 63) / 64 * 2;                // 32-column tiles the planes hold (rows padded to 64)
   const uint4* wp[2][C];
 #pragma unroll
@@ -79,7 +96,11 @@ __global__ __launch_bounds__(64, MAXW) void gemm_free_kernel(GemmArgs a) {
       for (int j = 0; j < C; ++j) wr[slot][p][j] = wp[p][j][(size_t)ks * 64];
   };
   auto step = [&](int slot) {
-    const float x[8] = {xr[slot][0][0], xr[slot][0][1], xr[slot][0][2], xr[slot][0][3], xr[slot][1][0], xr[slot][1][1], xr[slot][1][2], xr[slot][1][3]};
+    float x[8] = {xr[slot][0][0], xr[slot][0][1], xr[slot][0][2], xr[slot][0][3], xr[slot][1][0], xr[slot][1][1], xr[slot][1][2], xr[slot][1][3]};
+    if constexpr (RS) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) x[i] = ldexpf(x[i], -e);
+    }
     f16x8 xh, xl;
     split8(x, xh, xl);
     // the two small products first; consecutive MFMAs go to different accumulators
@@ -93,6 +114,7 @@ __global__ __launch_bounds__(64, MAXW) void gemm_free_kernel(GemmArgs a) {
   if constexpr (KS > 0) {
 #pragma unroll
     for (int d = 0; d < PD; ++d) if (d < KS) fetch(d, d);
+    if constexpr (RS) row_exponent();
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       // the fetches stay AHEAD of the step: without the fences the scheduler sinks every load to just before its use (s_waitcnt vmcnt(0)
@@ -104,6 +126,7 @@ __global__ __launch_bounds__(64, MAXW) void gemm_free_kernel(GemmArgs a) {
     }
   } else {
     for (int d = 0; d < PD; ++d) if (d < ksteps) fetch(d, d);
+    if constexpr (RS) row_exponent();
     for (int k3 = 0; k3 < ksteps; k3 += PD + 1) {
 #pragma unroll
       for (int u = 0; u <= PD; ++u) {
@@ -115,6 +138,12 @@ __global__ __launch_bounds__(64, MAXW) void gemm_free_kernel(GemmArgs a) {
         __builtin_amdgcn_sched_barrier(0);
       }
     }
+  }
+  if constexpr (RS) {
+#pragma unroll
+    for (int j = 0; j < C; ++j)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) acc[j][q] = ldexpf(acc[j][q], e);
   }
   // epilogue: register q of tile j = output column n0 + 32 j + 8 (q >> 2) + 4 kg + (q & 3) of row m0 + c
   if (row >= a.M) return;
@@ -176,28 +205,38 @@ __global__ __launch_bounds__(64, MAXW) void gemm_free_kernel(GemmArgs a) {
     }
 }
 
-template <int C, int PD, int MAXW>
+template <int C, int PD, int MAXW, bool RS = false>
 inline int launch_gemm_free_t(hipStream_t st, const GemmArgs& a) {
   const int ncb = (a.N + 32 * C - 1) / (32 * C), nrb = (a.M + 31) / 32;
   const dim3 grid((unsigned)((nrb + 7) / 8 * 8 * ncb)), block(64);
+  auto go = [&](auto ks) {
+    constexpr int KS = decltype(ks)::value;
+    hipLaunchKernelGGL((gemm_free_kernel<KS, C, PD, MAXW, RS>), grid, block, 0, st, a);
+  };
   switch (a.K / 16) {
-    case 2: hipLaunchKernelGGL((gemm_free_kernel<2, C, PD, MAXW>), grid, block, 0, st, a); break;
-    case 6: hipLaunchKernelGGL((gemm_free_kernel<6, C, PD, MAXW>), grid, block, 0, st, a); break;
-    case 8: hipLaunchKernelGGL((gemm_free_kernel<8, C, PD, MAXW>), grid, block, 0, st, a); break;
-    case 16: hipLaunchKernelGGL((gemm_free_kernel<16, C, PD, MAXW>), grid, block, 0, st, a); break;
-    case 32: hipLaunchKernelGGL((gemm_free_kernel<32, C, PD, MAXW>), grid, block, 0, st, a); break;
-    case 48: hipLaunchKernelGGL((gemm_free_kernel<48, C, PD, MAXW>), grid, block, 0, st, a); break;      // (K = 768: the backward of a QKV projection)
-    default: hipLaunchKernelGGL((gemm_free_kernel<0, C, PD, MAXW>), grid, block, 0, st, a); break;
+    case 2: go(std::integral_constant<int, 2>{}); break;
+    case 6: go(std::integral_constant<int, 6>{}); break;
+    case 8: go(std::integral_constant<int, 8>{}); break;
+    case 16: go(std::integral_constant<int, 16>{}); break;
+    case 32: go(std::integral_constant<int, 32>{}); break;
+    case 48: go(std::integral_constant<int, 48>{}); break;      // (K = 768: the backward of a QKV projection)
+    default: go(std::integral_constant<int, 0>{}); break;
   }
   return GLAMR_OK;
 }
 inline int launch_gemm_free(hipStream_t st, const GemmArgs& a) {
   if ((a.x_frag && a.ldx % 16 != 0) || (a.y_frag && (a.ldy % 16 != 0 || (a.R && a.ldr % 16 != 0) || a.ldy < (a.N + 3) / 4 * 4)))
     return fail(GLAMR_E_INVALID, "fragment-major GEMM: ldx=%d / ldy=%d / ldr=%d must be multiples of 16", a.ldx, a.ldy, a.ldr);
-  // few rows (the backward products of the taped infiller: 50 rows on an otherwise idle chip): ONE column tile per wave -- twice the waves, half the
+  // few row-major rows (50-row windows on an otherwise idle chip; the backward products below take the same tiles): ONE column tile per wave -- twice the waves, half the
   // chain of MFMAs in each (every output element is the same sum in the same order: bits unchanged)
   if (a.M <= 128 && !a.x_frag && !a.y_frag) return launch_gemm_free_t<1, 1, 4>(st, a);
   return launch_gemm_free_t<2, 1, 4>(st, a);      // column tiles per wave, k steps of operands ahead, waves per SIMD the allocation aims at
+}
+// the backward products of the taped infiller (row-major gradient rows, any number of them): the RS instances, the same tiles as above
+inline int launch_gemm_free_bwd(hipStream_t st, const GemmArgs& a) {
+  if (a.x_frag || a.y_frag) return fail(GLAMR_E_INVALID, "backward GEMM: row-major operands only");
+  if (a.M <= 128) return launch_gemm_free_t<1, 1, 4, true>(st, a);
+  return launch_gemm_free_t<2, 1, 4, true>(st, a);
 }
 
 // Y[row] = LayerNorm(X[row] (+ R[row])) over 256 columns (add_layernorm_kernel's two-pass arithmetic), all three fragment-major; one wave per
