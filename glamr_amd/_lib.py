@@ -2,7 +2,7 @@
 fails, a RuntimeError is raised -- the product path never computes on the CPU."""
 import ctypes
 import os
-from ctypes import c_int, c_int32, c_int64, c_size_t, c_uint32, c_float, c_double, c_void_p, c_char_p, POINTER, Structure
+from ctypes import c_int, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_float, c_double, c_void_p, c_char_p, POINTER, Structure
 
 _LIB = None
 LIB_PATH = os.environ.get('GLAMR_LIB_PATH') or os.path.join(os.path.dirname(os.path.abspath(__file__)), 'libglamr_hip.so')      # (override: A/B runs of kernel variants, tools/README.md)
@@ -103,6 +103,11 @@ _SIGNATURES = {
     'glamr_eval_regress_joints': (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'glamr_eval_procrustes': (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'glamr_eval_heading_align': (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'glamr_rng_bits': (c_int, [c_uint64, c_uint64, c_uint32, c_uint32, c_int64, c_void_p, c_void_p]),
+    'glamr_rng_normal': (c_int, [c_uint64, c_uint64, c_uint32, c_uint64, c_int64, c_void_p, c_void_p]),
+    'glamr_rng_box_muller': (c_int, [c_int64, c_void_p, c_void_p, c_void_p]),
+    'glamr_latents_draw': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'glamr_rng_set_seed': (c_int, [c_void_p, c_uint64, c_void_p]),
 }
 
 

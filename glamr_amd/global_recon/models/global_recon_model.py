@@ -23,6 +23,7 @@ import torch
 from ... import _lib
 from ...lib.models.smpl import SMPL, SMPL_MODEL_DIR
 from ...lib.utils import np_transform as nt
+from ...models import latent_rng
 from ...models.prior_models import MotionTrajJointModel
 from ...models.priors import num_windows, NZ
 from .. import packing
@@ -167,13 +168,18 @@ class PipelineGate:
 
 class ResidentGraph:
     """A captured optimize_resident step (GlobalReconOptimizer.capture_resident): one HIP graph, or -- under a PipelineGate -- two, split
-    where the gate's event is recorded (an event shared with another stream's graph cannot live inside a captured graph)."""
+    where the gate's event is recorded (an event shared with another stream's graph cannot live inside a captured graph).  A step captured under
+    latent_source 'philox' holds the latent draw but not its seed: every replay() first writes the model's `latent_seed` AS IT IS AT REPLAY TIME
+    to the batch's seed word on this stream (`before_replay`), so the seed may change between replays without re-capture."""
 
     def __init__(self, graph, datas, packed, stream, tail=None, gate=None, head=None):
         self.graph, self.datas, self.packed, self.stream, self.tail, self.gate, self.head = graph, datas, packed, stream, tail, gate, head
+        self.before_replay = None                 # set by capture_resident under latent_source 'philox' (see the class docstring)
 
     def replay(self):
         with torch.cuda.stream(self.stream):
+            if self.before_replay is not None:
+                self.before_replay()
             if self.head is not None:
                 self.head.replay()                                    # what precedes the priors does not wait for the gate (GLAMR_GATE_PREP=early)
             if self.gate is not None:
@@ -197,6 +203,11 @@ class GlobalReconOptimizer:
             raise RuntimeError('glamr_amd.GlobalReconOptimizer runs on an MI355X (device %r given); there is no CPU fallback' % (device,))
         _lib.lib()                                                     # fail early and loudly if the HIP library is missing
         self.pipeline_gate = None                                      # a PipelineGate when the caller alternates batches between two streams
+        # Where the priors' Gaussian latents come from when the caller gives none.  'torch': torch.randn on the global generator, the reference's
+        # source -- a person's draw then depends on its slot in the batch.  'philox': the library's counter-based streams (csrc/rng.hip,
+        # DESIGN.md 10): a function of (latent_seed, sequence id, person id, prior, element) alone, whatever batch, shard or padding.
+        self._latent_source = 'torch'
+        self.latent_seed = 0
         self._capture_split = None
         self._capture_head_split = None
         # Per-iteration loss log (:564,646-659).  The reference calls write_logs after EVERY optimizer.step -- with `log` None it prints.  Here
@@ -251,6 +262,38 @@ class GlobalReconOptimizer:
         self.smpl = smpl if smpl is not None else SMPL(SMPL_MODEL_DIR, pose_type='body26fk', create_transl=False).to(self.device)
         self.mt_model = mt_model if mt_model is not None else MotionTrajJointModel(None, self.device, log, smpl=self.smpl, results_root=results_root)
         self.timings = {}
+
+    @property
+    def latent_source(self):
+        return self._latent_source
+
+    @latent_source.setter
+    def latent_source(self, value):
+        self._latent_source = latent_rng.check_source(value)
+
+    def _latent_table(self, rin):
+        """latent_source 'philox': the per-slot (sequence id, person id) table of a staged batch and the seed word its draw kernel reads, on the
+        device (person id -1 = an empty slot of a scene with fewer persons than the batch maximum: its draws are zeros)."""
+        seq_ids, person_ids = [], []
+        for si, m in enumerate(rin.meta):
+            # (an explicit in_dict['seq_id'] was noted by stage_inputs whatever the source was then: a batch staged under 'torch' draws the same)
+            sid = latent_rng.seq_id_for(dict(seq_name=m['seq_name'], seq_id=(getattr(rin, 'explicit_seq_ids', None) or [None] * len(rin.meta))[si]))
+            for pi in range(rin.P):
+                seq_ids.append(sid)
+                person_ids.append(latent_rng.person_id_of(rin.ids[si][pi]) if pi < len(rin.ids[si]) else -1)
+        rin.latent_seq_ids, rin.latent_person_ids = latent_rng.slot_table(seq_ids, person_ids, self.device)
+        rin.latent_seed_word = latent_rng.new_seed_word(self.device)
+
+    def _draw_latents(self, rin, meps, teps):
+        """glamr_latents_draw into (meps, teps) on the current stream.  Outside a capture the seed word is written first; a captured step holds
+        the draw only and ResidentGraph.replay() writes the seed (so the seed can change between replays without re-capture)."""
+        if getattr(rin, 'latent_seq_ids', None) is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("this batch was staged under latent_source 'torch': stage_inputs() it again under 'philox' before capturing")
+            self._latent_table(rin)
+        if not torch.cuda.is_current_stream_capturing():
+            latent_rng.set_seed(rin.latent_seed_word, self.latent_seed)
+        latent_rng.draw_into(rin.latent_seed_word, rin.latent_seq_ids, rin.latent_person_ids, meps.shape[1], meps, teps)
 
     # ------------------------------------------------------------------------------------------------------------------------
     # host preprocessing of one person (global_recon_model.py:88-148)
@@ -417,6 +460,9 @@ class GlobalReconOptimizer:
                 meps[k, :m.shape[0]] = m
                 teps[k] = np.asarray(latents[si][idx]['traj'], np.float32).reshape(-1)
             meps, teps = torch.from_numpy(meps).to(dev), torch.from_numpy(teps).to(dev)
+        elif self.latent_source == 'philox':
+            sids = [latent_rng.seq_id_for(d) for d in in_dicts]
+            meps, teps = latent_rng.draw(self.latent_seed, [sids[si] for si, _, _ in flat], [latent_rng.person_id_of(idx) for _, idx, _ in flat], nw, dev)
         else:
             meps, teps = torch.randn((len(flat), nw, NZ), device=dev), torch.randn((len(flat), NZ), device=dev)
         t1 = time.time()
@@ -576,6 +622,10 @@ class GlobalReconOptimizer:
                     teps[si * P + pi] = np.asarray(latents[si][idx]['traj'], np.float32).reshape(-1)
             rin.meps, rin.teps = torch.from_numpy(meps).to(dev), torch.from_numpy(teps).to(dev)
         rin.meta = [{'seq_name': d['seq_name'], 'seq_len': Ts[si], 'gt': d.get('gt', {}), 'gt_meta': d.get('gt_meta', {})} for si, d in enumerate(in_dicts)]
+        rin.latent_seq_ids = rin.latent_person_ids = rin.latent_seed_word = None
+        rin.explicit_seq_ids = [d.get('seq_id') for d in in_dicts]
+        if self.latent_source == 'philox' and latents is None:
+            self._latent_table(rin)                          # (uploaded with the rest of the batch: before `upload_done`)
         # one event for "uploaded", on the stream this call ran on: the staging set is rewritten only after it and a pipelined caller's compute
         # stream waits for it.  The VALUE checks of the wire format run on the device later, on the stream that consumes the batch
         # (value_checks(), called by init_resident): as kernels of the upload stream they gated `upload_done` while competing for CUs with
@@ -718,9 +768,14 @@ class GlobalReconOptimizer:
             if rin.meps is not None:
                 meps.copy_(rin.meps)
                 teps.copy_(rin.teps)
+            elif self.latent_source == 'philox':
+                self._draw_latents(rin, meps, teps)
             else:
                 torch.randn(meps.shape, out=meps)
                 torch.randn(teps.shape, out=teps)
+        elif rin.meps is None and self.latent_source == 'philox':
+            meps, teps = torch.empty((n_slots, nw, NZ), device=dev), torch.empty((n_slots, NZ), device=dev)
+            self._draw_latents(rin, meps, teps)
         else:
             meps = rin.meps if rin.meps is not None else torch.randn((n_slots, nw, NZ), device=dev)
             teps = rin.teps if rin.teps is not None else torch.randn((n_slots, NZ), device=dev)
@@ -1037,6 +1092,8 @@ class GlobalReconOptimizer:
         # the value checks of the wire format run once per batch, outside a capture (init_resident skips them while capturing): a batch whose
         # FIRST use is this capture is checked here -- the verdict surfaces in collect() / check_inputs() as usual
         self.value_checks(rin)
+        if self.latent_source == 'philox' and rin.meps is None and getattr(rin, 'latent_seq_ids', None) is None:
+            self._latent_table(rin)                                   # (a batch staged under 'torch': its table is uploaded here, outside the capture)
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
         if st == torch.cuda.default_stream(self.device):
             st = torch.cuda.Stream(device=self.device)               # the legacy default stream cannot be captured
@@ -1083,16 +1140,22 @@ class GlobalReconOptimizer:
                     self._capture_head_split = None
                 tail.capture_end()
             rg = ResidentGraph(graph, datas, packed, st, tail=tail, gate=self.pipeline_gate, head=head)
+        philox = getattr(rin, 'latent_seed_word', None) is not None and rin.meps is None and self.latent_source == 'philox'
+        if philox:
+            # the captured draw reads its seed from the batch's seed word: every replay first writes the model's CURRENT latent_seed there
+            rg.before_replay = lambda: latent_rng.set_seed(rin.latent_seed_word, self.latent_seed)
         if check:
             torch.cuda.synchronize(self.device)
             with torch.random.fork_rng(devices=[self.device]):          # the caller's generators are left as they were
                 seed = 20260926
-                torch.manual_seed(seed)
+                if not philox:                                          # ('philox': both sides write self.latent_seed to the seed word instead)
+                    torch.manual_seed(seed)
                 with torch.cuda.stream(st):
                     _, ref = self.optimize_resident(rin, max_iters)
                 torch.cuda.synchronize(self.device)
                 want = ref.t['kp_2d_pred'].clone()
-                torch.manual_seed(seed)
+                if not philox:
+                    torch.manual_seed(seed)
                 rg.replay()
                 torch.cuda.synchronize(self.device)
             got = packed.t['kp_2d_pred']

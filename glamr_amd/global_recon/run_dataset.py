@@ -60,6 +60,10 @@ def build_parser():
     ap.add_argument('--seqs', nargs='+', default=None, help='extension: sequences to run (default: the test sequences of --dataset)')
     ap.add_argument('--gt_dir', default=None, help="extension: ground-truth directory (default: the dataset's gt_pose path when it exists)")
     ap.add_argument('--gpus', type=int, default=1, help='extension: shard the sequences over N GPUs of this node, one process per GPU (rank r uses GPU r; --gpu is the single-process device)')
+    ap.add_argument('--latent_rng', choices=('torch', 'philox'), default='torch',
+                    help="extension: source of the priors' latent draws.  torch: torch.randn seeded per --seeds value (the reference's; a sequence's draws "
+                         'depend on its place in the batch, hence on --gpus, --seqs and --cached); philox: per-sequence counter-based streams of the library '
+                         'with the --seeds value as their seed -- the same sequence gets the same draws however the run is sharded')
     ap.add_argument('--backend', default=None, help='extension: torch.distributed backend of --gpus N (default nccl = RCCL)')
     ap.add_argument('--stub-model', action='store_true', help=argparse.SUPPRESS)      # CPU stand-ins for the optimiser and the evaluator: tests of the sharding protocol over gloo
     return ap
@@ -159,6 +163,7 @@ def main(argv=None):
     for seed in seeds:
         np.random.seed(seed)
         torch.manual_seed(seed)
+        model.latent_source, model.latent_seed = args.latent_rng, seed
         files = [os.path.join(args.out_dir, seq, 'grecon', '%s_seed%d.pkl' % (seq, seed)) for seq in seqs]
         todo = [i for i, f in enumerate(files) if not (args.cached and os.path.exists(f))]
         outs = dict(zip(todo, model.optimize_batch([in_dicts[i] for i in todo]))) if todo else {}

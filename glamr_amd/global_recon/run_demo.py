@@ -37,6 +37,9 @@ def build_parser():
     ap.add_argument('--vis', action='store_true', default=False)
     ap.add_argument('--vis_cam', action='store_true', default=False)
     ap.add_argument('--save_video', action='store_true', default=False)
+    ap.add_argument('--latent_rng', choices=('torch', 'philox'), default='torch',
+                    help="extension: source of the priors' latent draws.  torch: torch.randn seeded with --seed (the reference's); philox: the library's "
+                         'per-sequence counter-based streams with --seed as their seed -- the draws depend on (seed, sequence name, person) alone')
     ap.add_argument('--seq_name', default=None, help='extension: name of the result file (default: the video file name, else the last component of --out_dir)')
     return ap
 
@@ -87,6 +90,7 @@ def main(argv=None):
         torch.cuda.set_device(args.gpu)
         in_dict = wire.load_pose_pkl(pose_file, seq_name=seq_name)
         model = model_dict[cfg.get('grecon_model_name', 'global_recon_model')](cfg, device, None)
+        model.latent_source, model.latent_seed = args.latent_rng, args.seed
         out_dict = model.optimize(in_dict)
         os.makedirs(os.path.dirname(out_file), exist_ok=True)
         with open(out_file, 'wb') as f:

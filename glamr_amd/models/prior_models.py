@@ -20,6 +20,7 @@ import torch
 from .layouts import INFILLER_LAYOUT, TRAJPRED_LAYOUT
 from .priors import MotionPriorsHandle, num_windows, local_to_global, NZ, PAST, CUR, VAE_INFER, VAE_TRAIN, VAE_RECON
 from ..lib.utils.dist import Normal
+from . import latent_rng
 
 FUT = 10
 SMPL_PARENTS = [-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19, 20, 21]
@@ -78,6 +79,16 @@ class _PriorBase:
     def _randn(self, shape):
         dev = self.device if self.noise_device is None else torch.device(self.noise_device)
         return torch.randn(shape, device=dev).to(self.device)
+
+    # Source of the draws `.inference` makes when the batch carries no latents: 'torch' (torch.randn, the reference's) or 'philox' -- the
+    # library's counter-based streams (latent_rng) under `latent_seed`: row b of the batch is the sequence (its entry of `seq_id`,
+    # else its `seq_name` entry hashed, else the row index), sample k plays the person id, counted from the row's `person_id` entry when the batch
+    # has one (latent_rng.batch_ids).  (`forward(data)`, the training pass, stays on torch.)
+    latent_source = 'torch'
+    latent_seed = 0
+
+    def _philox(self):
+        return latent_rng.check_source(self.latent_source) == 'philox'
 
     def __call__(self, data):
         return self.forward(data)
@@ -205,7 +216,12 @@ class MotionInfillerVAE(_PriorBase):
             w['vis_frame_mask'] = rep(data['vis_frame_mask'], 0)
             if 'pose_tp' in data:
                 w['pose_tp'] = rep(data['pose_tp'], 1)
-            eps = data['in_motion_latent'].to(self.device).float() if 'in_motion_latent' in data else self._randn((B * sample_num, self.nz))
+            if 'in_motion_latent' in data:
+                eps = data['in_motion_latent'].to(self.device).float()
+            elif self._philox():
+                eps = latent_rng.draw_samples(self.latent_seed, batch, B, sample_num, 1, self.device)[0].reshape(B * sample_num, self.nz)
+            else:
+                eps = self._randn((B * sample_num, self.nz))
             if eps.shape[0] != B * sample_num:
                 eps = eps.expand(B * sample_num, -1)
             self._window_pass(w, VAE_INFER, eps=eps.contiguous(), _handle=h)
@@ -231,9 +247,12 @@ class MotionInfillerVAE(_PriorBase):
         B, T = pose.shape[:2]
         nw = num_windows(T)
         outs = []
-        for _ in range(sample_num):
+        drawn = latent_rng.draw_samples(self.latent_seed, batch, B, sample_num, nw, self.device)[0] if 'in_motion_latent' not in batch and self._philox() else None
+        for si in range(sample_num):
             if 'in_motion_latent' in batch:
                 eps = batch['in_motion_latent'].to(self.device).float().view(1, nw, NZ).expand(B, -1, -1).contiguous()
+            elif drawn is not None:
+                eps = drawn[:, si].contiguous()
             else:
                 eps = self._randn((B, nw, NZ))
             outs.append(h.infer(pose.contiguous(), vis, [T] * B, motion_eps=eps, traj=False)['pose'])
@@ -373,10 +392,13 @@ class TrajPredVAE(_PriorBase):
                 data['recon_out_pose_tp'] = torch.cat([data['recon_out_orient_tp'], data['in_body_pose_tp']], dim=-1)
                 data['recon_out_pose'] = data['recon_out_pose_tp'].transpose(1, 0).contiguous()
 
-    def _eps_infer(self, batch, B, sample_num):
+    def _eps_infer(self, batch, B, sample_num, chunk=0):
         if 'in_traj_latent' in batch:
             e = batch['in_traj_latent'].to(self.device).float()
             return (e.expand(B * sample_num, -1) if e.shape[0] != B * sample_num else e).contiguous()
+        if self._philox():
+            # chunk c of the chunked inference draws elements [128 c, 128 (c + 1)) of the row's trajectory stream
+            return latent_rng.traj_chunk_samples(self.latent_seed, batch, B, sample_num, chunk, self.device).reshape(B * sample_num, self.nz)
         return self._randn((B * sample_num, self.nz))
 
     def _multi_step(self, batch, sample_num, recon, _handle=None):
@@ -400,7 +422,7 @@ class TrajPredVAE(_PriorBase):
                     v = torch.cat([v, torch.zeros((e - eb,) + v.shape[1:], device=v.device, dtype=v.dtype)], dim=0)
                 c[k] = v
             S = 1 if recon else sample_num
-            self._clip_pass(c, mode, eps=None if recon else self._eps_infer(batch, data['batch_size'], sample_num), sample_num=S, _handle=_handle)
+            self._clip_pass(c, mode, eps=None if recon else self._eps_infer(batch, data['batch_size'], sample_num, chunk=i), sample_num=S, _handle=_handle)
             nf = eb - s
             if rows is None:
                 rows = c[name + '_out_local_traj_tp'][:nf]
@@ -441,8 +463,12 @@ class TrajPredVAE(_PriorBase):
             pose = batch['in_body_pose'].to(self.device).float()
             B, T = pose.shape[:2]
             res = {k: [] for k in ('local_traj', 'trans', 'orient')}
-            for _ in range(sample_num):
-                eps = batch['in_traj_latent'].to(self.device).float().expand(B, -1).contiguous() if 'in_traj_latent' in batch else self._randn((B, NZ))
+            drawn = latent_rng.draw_samples(self.latent_seed, batch, B, sample_num, 0, self.device)[1] if 'in_traj_latent' not in batch and self._philox() else None
+            for si in range(sample_num):
+                if drawn is not None:
+                    eps = drawn[:, si].contiguous()
+                else:
+                    eps = batch['in_traj_latent'].to(self.device).float().expand(B, -1).contiguous() if 'in_traj_latent' in batch else self._randn((B, NZ))
                 o = h.infer(pose, None, [T] * B, traj_eps=eps, infill=False)
                 for k in res:
                     res[k].append(o[k])
@@ -505,6 +531,23 @@ class MotionTrajJointModel:
         self.handle = MotionPriorsHandle(self.mfiller._sd, self.traj_predictor._sd, smpl.rest_joints(), SMPL_PARENTS, self.device)
         self.mfiller._handle = self.traj_predictor._handle = self.handle          # one set of device weights serves all three classes
 
+    # latent_source / latent_seed of the wrapper are those of both priors (see _PriorBase)
+    @property
+    def latent_source(self):
+        return self.mfiller.latent_source
+
+    @latent_source.setter
+    def latent_source(self, value):
+        self.mfiller.latent_source = self.traj_predictor.latent_source = latent_rng.check_source(value)
+
+    @property
+    def latent_seed(self):
+        return self.mfiller.latent_seed
+
+    @latent_seed.setter
+    def latent_seed(self, value):
+        self.mfiller.latent_seed = self.traj_predictor.latent_seed = int(value)
+
     def get_motion_latent(self, seq_len):
         return self.mfiller.get_latent(seq_len)
 
@@ -535,6 +578,11 @@ class MotionTrajJointModel:
             if mode == 'infer':
                 motion = motion.reshape(-1, *motion.shape[-2:])
                 batch = {'in_body_pose': motion}
+                if self.traj_predictor._philox() and 'in_traj_latent' not in data:
+                    # rows here are (row, sample) pairs of one sample each: the predictor must draw the stream of THAT pair (latent_rng.batch_ids)
+                    sids, base = latent_rng.batch_ids(data, motion.shape[0] // sample_num)
+                    batch['seq_id'] = [s for s in sids for _ in range(sample_num)]
+                    batch['person_id'] = [p + k for p in base for k in range(sample_num)]
                 if 'in_traj_latent' in data:
                     batch['in_traj_latent'] = data['in_traj_latent']
                 if 'init_xy' in data:
@@ -565,11 +613,13 @@ class MotionTrajJointModel:
         B, T = pose.shape[:2]
         nw = num_windows(T)
         res = {k: [] for k in ('pose', 'local_traj', 'trans', 'orient')}
-        for _ in range(sample_num):
+        philox = latent_rng.check_source(self.latent_source) == 'philox' and not ('in_motion_latent' in batch and 'in_traj_latent' in batch)
+        dm, dt = latent_rng.draw_samples(self.latent_seed, batch, B, sample_num, nw, self.device) if philox else (None, None)
+        for si in range(sample_num):
             me = batch['in_motion_latent'].to(self.device).float().view(1, nw, NZ).expand(B, -1, -1).contiguous() if 'in_motion_latent' in batch \
-                else torch.randn((B, nw, NZ), device=self.device)
+                else dm[:, si].contiguous() if philox else torch.randn((B, nw, NZ), device=self.device)
             te = batch['in_traj_latent'].to(self.device).float().expand(B, -1).contiguous() if 'in_traj_latent' in batch \
-                else torch.randn((B, NZ), device=self.device)
+                else dt[:, si].contiguous() if philox else torch.randn((B, NZ), device=self.device)
             o = self.handle.infer(pose, vis, [T] * B, motion_eps=me, traj_eps=te)
             for k in res:
                 res[k].append(o[k])

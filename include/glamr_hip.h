@@ -454,6 +454,31 @@ int glamr_eval_procrustes(int n, int n_joints, const float* S1, const float* S2,
 int glamr_eval_heading_align(int n, int align_freq, const float* orient_aa, const float* trans, float* aligned_orient_aa, float* aligned_trans,
                              float* aligned_orient_q, void* stream);
 
+/* ---- the priors' Gaussian latent draws from per-sequence Philox4x32-10 streams (csrc/rng_algo.hpp, csrc/rng.hip) ------------
+ * Replaces the reference's `torch.randn` draws (lib/utils/dist.py:21-23 through motion_infiller_vae.py / traj_pred_vae.py): every number is a
+ * function of (seed, seq_id, sub, element index) alone.  key = seed (low word first); counter = (block, sub, seq_id low, seq_id high);
+ * element e of a stream is word e % 4 of block e / 4; sub = 2 * person_id + prior (0 = motion infiller, 1 = trajectory predictor); normals by
+ * Box-Muller on the word pairs (0,1), (2,3): u = (x + 0.5) 2^-32, theta = 2 pi (y + 0.5) 2^-32 -> sqrt(-2 ln u) (cos theta, sin theta).
+ * `block` is the only block counter: a range that would pass 2^32 blocks (2^34 values) is refused with GLAMR_E_INVALID, never carried into
+ * `sub`.  A count of 0 is a no-op; null pointers and negative counts return GLAMR_E_INVALID before any HIP call.
+ * glamr_rng_bits: the raw words of blocks [first_block, first_block + n_blocks): out dev (n_blocks, 4) uint32, 16-byte aligned.
+ * glamr_rng_normal: the n normals of elements [first_elem, first_elem + n) into out dev (n) fp32 (any 4-byte alignment, any first_elem and
+ *   n; nothing outside [out, out + n) is written): consecutive calls concatenate to exactly what one call gives.
+ * glamr_rng_box_muller: the uniform -> normal map of the kernels above on words the caller chose: bits dev (n_blocks, 4) uint32 -> out dev
+ *   (n_blocks, 4) fp32, both 16-byte aligned (for checking the map at the ends of the range, e.g. x = 0 and x = 0xffffffff).
+ * glamr_latents_draw: both latent arrays of a batch in ONE launch: per slot s with person_ids[s] >= 0, meps[s] (n_windows, 128) = elements
+ *   [0, n_windows * 128) of stream (seq_ids[s], 2 * person_ids[s]) and teps[s] (128) = elements [0, 128) of stream (seq_ids[s],
+ *   2 * person_ids[s] + 1); a slot with person_ids[s] < 0 is padding and is written as zeros.  All pointers dev; meps (n_slots, n_windows, 128)
+ *   and teps (n_slots, 128) 16-byte aligned.  The seed is READ FROM DEVICE MEMORY (seed_dev: one uint64) when the kernel runs, so a captured
+ *   step is replayed under another seed by rewriting that word, without re-capture:
+ * glamr_rng_set_seed: writes `seed` to seed_dev (dev) in stream order (a one-thread kernel; the value travels as a launch argument). */
+int glamr_rng_bits(uint64_t seed, uint64_t seq_id, uint32_t sub, uint32_t first_block, int64_t n_blocks, uint32_t* out, void* stream);
+int glamr_rng_normal(uint64_t seed, uint64_t seq_id, uint32_t sub, uint64_t first_elem, int64_t n, float* out, void* stream);
+int glamr_rng_box_muller(int64_t n_blocks, const uint32_t* bits, float* out, void* stream);
+int glamr_latents_draw(const uint64_t* seed_dev, const uint64_t* seq_ids, const int32_t* person_ids, int n_slots, int n_windows, float* meps,
+                       float* teps, void* stream);
+int glamr_rng_set_seed(uint64_t* seed_dev, uint64_t seed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
