@@ -170,7 +170,7 @@ struct glamr_nets {
   // fp16's range the handle runs the plain fp32 kernels everywhere (fp32_only): slower, never wrong.
   bool fp32_only = false;
   double worst_activation = 0, worst_weight = 0;
-  std::map<const Lin*, Lin> lin_T;      // transposed weights of the layers the infiller's backward multiplies with (nets_tape.inc), made on first use
+  std::map<const Lin*, Lin> lin_T;      // transposed weights of the layers the infiller's backward multiplies with (nets_tape.hpp), made on first use
 };
 constexpr size_t GRAPH_CACHE_MAX = 24, CAPTURE_LENS_INTS = 256 * 1024;
 
@@ -348,11 +348,40 @@ struct Ws {
   unsigned char* mask; int* lens; int* lens2;
   size_t total; int Tpad;
 };
+// windows [30 i, 30 i + 50) that generate every frame of a sequence of `len` frames (motion_infiller_vae.py:625); the pose buffer of a batch
+// is padded so that the last window of the longest possible sequence lies inside it
+constexpr int windows_of(int len) { return (len - PAST + CUR - 1) / CUR; }
+constexpr int tpad_of(int max_len) { return std::max(max_len, (std::max(1, windows_of(max_len)) - 1) * CUR + WIN); }
+
+// the activation slots of one infiller window (infiller_window below writes them, taped_window_bwd of nets_tape.hpp reads them): distinct
+// buffers in a tape, aliases of the few workspace buffers otherwise (window_slots)
+struct EncTape { float *qkv, *att, *tmp1, *mid, *ff, *tmp2, *out; };
+struct DecTape { float *qkv, *att_s, *tmp_s, *xa, *qbuf, *ctxkv, *att_c, *tmp_c, *xb, *ff, *tmp_f, *xc; };
+struct WinTape {
+  float *x, *h0; EncTape enc[2];
+  float *p_ctxkv, *p_att, *p_tmp1, *p_x1, *p_a, *p_ff, *p_tmp2, *p_b, *pz, *z;
+  float *zproj, *q0; DecTape dec[2];
+  float *o1, *o2, *y;
+  unsigned char* mask;
+  float *gx, *q2, *qpz;      // posterior branch only (never taped)
+};
+// One window at a time through the workspace: every layer reuses the same scratch buffers, the encoder layers ping-pong h0 / h1 and everything
+// from the prior's token rows to the decoder's last layer works in place on w.dq.
+WinTape window_slots(const Ws& w) {
+  WinTape s{};
+  s.x = w.x; s.h0 = w.h0; s.mask = w.mask;
+  for (int l = 0; l < 2; ++l) { float* out = l == 0 ? w.h1 : w.h0; s.enc[l] = EncTape{w.qkv, w.att, w.tmp, out, w.ff, w.tmp, out}; }
+  s.p_ctxkv = w.ctxkv; s.p_att = w.att; s.p_tmp1 = s.p_tmp2 = w.tmp; s.p_x1 = s.p_a = s.p_b = w.dq; s.p_ff = w.ff; s.pz = w.pz; s.z = w.z;
+  s.zproj = w.zproj; s.q0 = w.dq;
+  for (DecTape& d : s.dec) d = DecTape{w.qkv, w.att, w.tmp, w.dq, w.qbuf, w.ctxkv, w.att, w.tmp, w.dq, w.ff, w.tmp, w.dq};
+  s.o1 = w.ff; s.o2 = w.tmp; s.y = w.y;
+  s.gx = w.gx; s.q2 = w.q2; s.qpz = w.qpz;
+  return s;
+}
+
 Ws ws_layout(int B, int max_len, char* base) {
   Ws w{};
-  int nwin = (max_len - PAST + CUR - 1) / CUR;
-  if (nwin < 1) nwin = 1;
-  w.Tpad = std::max(max_len, (nwin - 1) * CUR + WIN);
+  w.Tpad = tpad_of(max_len);
   size_t off = 0;
   auto take = [&](size_t nfloats) { float* p = reinterpret_cast<float*>(base + off); off = align_up(off + (nfloats + 32 * 1024) * sizeof(float), 256); return p; };      // (+ 32 rows: the fragment-major kernels of nn_free.hpp work in whole 32-row blocks)
   const size_t MW = (size_t)B * WIN, MT = (size_t)B * max_len;
@@ -373,13 +402,16 @@ Ws ws_layout(int B, int max_len, char* base) {
 
 #define RC(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
 
-// set by every entry point from its handle: 1 = the plain fp32 kernels only (range analysis of glamr_nets_create)
-thread_local int tl_fp32 = 0;
-// set by every entry point from the batch size: 1 = the LDS-free one-wave kernels of nn_free.hpp, which run beside resident workgroups of
-// the optimiser stage (large batches: the other stream of a pipelined caller is inside a stage launch most of the time);
-// GLAMR_NETS_FREE=0 keeps the fused LDS kernels (A/B runs)
-thread_local int tl_free = 0;
-inline size_t cp(int col) { return tl_free ? (size_t)col * 32 : (size_t)col; }      // pointer offset of column `col` (a multiple of 16) in either layout
+// Which kernels a call runs on, and where: built once by each entry point, handed to every helper below.
+struct Plan {
+  hipStream_t st;
+  bool fp32;      // the plain fp32 kernels only (the handle's range analysis, glamr_nets_create)
+  bool free;      // the LDS-free one-wave kernels of nn_free.hpp on fragment-major activations, which run beside resident workgroups of the
+                  // optimiser stage (large batches of glamr_nets_infer: the other stream of a pipelined caller is inside a stage launch most of
+                  // the time); GLAMR_NETS_FREE=0 keeps the fused LDS kernels (A/B runs)
+  bool keep;      // the caller keeps every activation (tape): never the fused row-block / QKV-attention kernels, which leave theirs on chip
+  size_t cp(int col) const { return free ? (size_t)col * 32 : (size_t)col; }      // pointer offset of column `col` (a multiple of 16) in either layout
+};
 inline bool free_wanted(int flags) {
   const char* e = std::getenv("GLAMR_NETS_FREE");      // read per call: A/B runs switch it inside one process
   return e ? std::atoi(e) != 0 : (flags & GLAMR_NETS_COSCHEDULE) != 0;
@@ -416,27 +448,32 @@ __global__ __launch_bounds__(64) void attention_f32_kernel(const float* Q, int l
   for (int d = 0; d < 32; ++d) O[(size_t)(b * Lq + lane) * ldo + h * 32 + d] = o[d];
 }
 
-template <class... A>
-void launch_attention(dim3 grid, dim3 block, size_t lds, hipStream_t st, const float* Q, int ldq, const float* K, const float* V, int ldk,
-                      const unsigned char* mask, float* O, int ldo, int Lq, int Lk, int q_shared) {
-  if (tl_fp32) hipLaunchKernelGGL(attention_f32_kernel, grid, dim3(64), 0, st, Q, ldq, K, V, ldk, mask, O, ldo, Lq, Lk, q_shared);
-  else if (tl_free) hipLaunchKernelGGL(attention_free_kernel, dim3(grid.x * 8), dim3(64), 0, st, Q, ldq, K, V, ldk, mask, O, ldo, Lq, Lk, q_shared);
-  else hipLaunchKernelGGL(attention_mfma_kernel, grid, block, lds, st, Q, ldq, K, V, ldk, mask, O, ldo, Lq, Lk, q_shared);
+// one (sequence, head) per workgroup -- resp. per wave of the LDS-free kernel -- for B sequences of Lq queries and Lk keys
+void launch_attention(const Plan& p, int B, const float* Q, int ldq, const float* K, const float* V, int ldk, const unsigned char* mask, float* O, int ldo,
+                      int Lq, int Lk, int q_shared) {
+  if (p.fp32) hipLaunchKernelGGL(attention_f32_kernel, dim3(B, 8), dim3(64), 0, p.st, Q, ldq, K, V, ldk, mask, O, ldo, Lq, Lk, q_shared);
+  else if (p.free) hipLaunchKernelGGL(attention_free_kernel, dim3(B * 8), dim3(64), 0, p.st, Q, ldq, K, V, ldk, mask, O, ldo, Lq, Lk, q_shared);
+  else hipLaunchKernelGGL(attention_mfma_kernel, dim3(B, 8), dim3(64), 0, p.st, Q, ldq, K, V, ldk, mask, O, ldo, Lq, Lk, q_shared);
 }
 
-int ln(hipStream_t st, const float* X, const float* R, const LN& n, float* Y, int rows) {
-  if (tl_free) { hipLaunchKernelGGL(ln_free_kernel, dim3((rows + 31) / 32), dim3(64), 0, st, X, R, n.g, n.b, Y, rows); return GLAMR_OK; }
-  hipLaunchKernelGGL(add_layernorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, X, R, n.g, n.b, Y, rows, D);
+int ln(const Plan& p, const float* X, const float* R, const LN& n, float* Y, int rows) {      // Y = LayerNorm(X (+ R)); Y may be X or R
+  if (p.free) { hipLaunchKernelGGL(ln_free_kernel, dim3((rows + 31) / 32), dim3(64), 0, p.st, X, R, n.g, n.b, Y, rows); return GLAMR_OK; }
+  hipLaunchKernelGGL(add_layernorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, p.st, X, R, n.g, n.b, Y, rows, D);
   return GLAMR_OK;
 }
 // the fused row-block / fused attention kernels from SMALL_ROWS rows on (nn_kernels.hpp); below it the launches are latency-bound either way:
 // separate small-M fp32 kernels
-inline bool fuse_attention(int M) { return !tl_fp32 && !tl_free && M >= SMALL_ROWS; }
-// Y = LayerNorm(X W^T + b + R): attention out-projection + residual + norm in one pass over the rows
-int proj_ln(hipStream_t st, const Lin& L, const LN& n, const float* X, const float* R, float* Y, float* tmp, int M);
-// Y = [LayerNorm](act2(relu(X W1^T + b1) W2^T + b2) [+ R]): feed-forward block / two-layer MLP with the hidden rows on chip
-int mlp2(hipStream_t st, const Lin& L1, const Lin& L2, const LN* n, const float* X, int ldx, const float* R, float* Y, float* hidden, float* tmp, int M,
-         int act2);
+inline bool fuse_attention(const Plan& p, int M) { return !p.fp32 && !p.free && !p.keep && M >= SMALL_ROWS; }
+
+// what a linear layer's call sets beyond the common form (lin below)
+struct LinOpt {
+  const float* R = nullptr; int ldr = 0;                        // residual rows, added after the activation
+  const float* rowbias = nullptr; int rpg = 1, ldrb = 0;       // bias row per group of rpg rows (rpg < 0: per position, row % -rpg), see GemmArgs
+  // free plans only: X, resp. Y and R, are row-major (what an LDS kernel or a small elementwise kernel produced / will consume) instead
+  // of fragment-major, the default there
+  bool x_rowmajor = false, y_rowmajor = false;
+  bool bwd = false;                                             // a backward product (gradient rows times a transposed weight)
+};
 
 // Few rows (a window of one sequence has 50: the latent-optimisation mode makes ~335 such products forward and ~335 backward per iteration):
 // the fp32 GEMM of round 5 walked K with v_mfma_f32_32x32x2_f32 on ONE accumulator per wave -- a chain of K / 2 dependent 64-cycle instructions, 3.4 us at
@@ -453,53 +490,52 @@ int mlp2(hipStream_t st, const Lin& L1, const Lin& L2, const LN* n, const float*
 // the motion latent moves by 3.8e-6 of its largest entry and, eight Adam steps later, the latent of one of the three reference fixtures is 9.5e-4
 // away instead of 1.4e-6 (Adam's first steps are sign-like: an entry whose gradient is ~0 takes a full step the other way) -- outside the 1e-4
 // tests/test_latent_gpu.py holds it to.
-int lin(hipStream_t st, const Lin& L, const float* X, int ldx, float* Y, int ldy, int M, int act = ACT_NONE, const float* R = nullptr, int ldr = 0,
-        const float* rowbias = nullptr, int rpg = 1, int ldrb = 0, int xl = -1, int yl = -1, bool bwd = false) {
-  // xl / yl (free mode only): layout of X, resp. Y and R -- 1 fragment-major (the default there), 0 row-major (what an LDS kernel or a small
-  // elementwise kernel produced / will consume)
-  if (tl_free && L.Ws && M > 0) {
+// Y = act(X W^T + b [+ row bias]) [+ R] on the plan's kernel family: the LDS-free kernel under a free plan, the row-scaled one-wave kernel for a
+// backward product, else launch_gemm's choice by the number of rows.  (A handle in fp32_only mode has no fp16 planes: L.Ws is null everywhere.)
+int lin(const Plan& p, const Lin& L, const float* X, int ldx, float* Y, int ldy, int M, int act = ACT_NONE, const LinOpt& o = {}) {
+  GemmArgs a{X, L.W, L.b, o.rowbias, o.R, Y, M, L.N, L.K, ldx, ldy, o.ldr, o.rpg, o.ldrb, act};
+  a.Ws = L.Ws;
+  a.ws_plane = (size_t)((L.N + 63) / 64 * 64) * L.K;
+  if (p.free && L.Ws && M > 0) {
     if (L.K % 32 != 0 || ldx % 4 != 0 || ldy % 4 != 0) return fail(GLAMR_E_INVALID, "gemm: K=%d must be a multiple of 32, ldx=%d / ldy=%d of 4", L.K, ldx, ldy);
-    GemmArgs a{X, L.W, L.b, rowbias, R, Y, M, L.N, L.K, ldx, ldy, ldr, rpg, ldrb, act};
-    a.Ws = L.Ws;
-    a.ws_plane = (size_t)((L.N + 63) / 64 * 64) * L.K;
-    a.x_frag = xl != 0;
-    a.y_frag = yl != 0;
-    return launch_gemm_free(st, a);
+    a.x_frag = !o.x_rowmajor;
+    a.y_frag = !o.y_rowmajor;
+    return launch_gemm_free(p.st, a);
   }
-  if (bwd && !tl_fp32 && L.Ws && M > 0) {
-    if (L.K % 32 != 0 || ldx % 4 != 0 || ldy % 4 != 0 || (R && ldr % 4 != 0) || rowbias)
-      return fail(GLAMR_E_INVALID, "backward gemm: K=%d must be a multiple of 32, ldx=%d / ldy=%d / ldr=%d of 4, no row bias", L.K, ldx, ldy, ldr);
-    GemmArgs a{X, L.W, L.b, rowbias, R, Y, M, L.N, L.K, ldx, ldy, ldr, rpg, ldrb, act};
-    a.Ws = L.Ws;
-    a.ws_plane = (size_t)((L.N + 63) / 64 * 64) * L.K;
-    return launch_gemm_free_bwd(st, a);                   // (row-major X, Y and R: x_frag = y_frag = 0)
+  if (o.bwd && !p.fp32 && L.Ws && M > 0) {
+    if (L.K % 32 != 0 || ldx % 4 != 0 || ldy % 4 != 0 || (o.R && o.ldr % 4 != 0) || o.rowbias)
+      return fail(GLAMR_E_INVALID, "backward gemm: K=%d must be a multiple of 32, ldx=%d / ldy=%d / ldr=%d of 4, no row bias", L.K, ldx, ldy, o.ldr);
+    return launch_gemm_free_bwd(p.st, a);                 // (row-major X, Y and R: x_frag = y_frag = 0)
   }
-  return launch_gemm(st, X, ldx, L.W, L.b, Y, ldy, M, L.N, L.K, act, R, ldr, rowbias, rpg, ldrb, L.Ws);
+  return launch_gemm(p.st, a);
 }
 
-int proj_ln(hipStream_t st, const Lin& L, const LN& n, const float* X, const float* R, float* Y, float* tmp, int M) {
-  if (!tl_free && M >= SMALL_ROWS && L.N == D && L.K == D && L.Ws)
-    return launch_rows(st, X, D, M, D, nullptr, 0, nullptr, nullptr, 1, 0, L.Ws, (size_t)D * L.K, L.K, L.b, ACT_NONE, R, D, n.g, n.b, Y, D);
-  if (tl_free) {      // the residual in the GEMM's epilogue (same sum, same order): the three-pass LayerNorm then streams ONE array
-    RC(lin(st, L, X, D, tmp, D, M, ACT_NONE, R, D));
-    return ln(st, tmp, nullptr, n, Y, M);
+// Y = LayerNorm(X W^T + b + R): attention out-projection + residual + norm in one pass over the rows; `tmp` holds the sum when the pass is not fused
+int proj_ln(const Plan& p, const Lin& L, const LN& n, const float* X, const float* R, float* Y, float* tmp, int M) {
+  if (!p.free && !p.keep && M >= SMALL_ROWS && L.N == D && L.K == D && L.Ws)
+    return launch_rows(p.st, X, D, M, D, nullptr, 0, nullptr, nullptr, 1, 0, L.Ws, (size_t)D * L.K, L.K, L.b, ACT_NONE, R, D, n.g, n.b, Y, D);
+  if (p.free) {      // the residual in the GEMM's epilogue (same sum, same order): the three-pass LayerNorm then streams ONE array
+    RC(lin(p, L, X, D, tmp, D, M, ACT_NONE, {.R = R, .ldr = D}));
+    return ln(p, tmp, nullptr, n, Y, M);
   }
-  RC(lin(st, L, X, D, tmp, D, M));
-  return ln(st, tmp, R, n, Y, M);
+  RC(lin(p, L, X, D, tmp, D, M));
+  return ln(p, tmp, R, n, Y, M);
 }
-int mlp2(hipStream_t st, const Lin& L1, const Lin& L2, const LN* n, const float* X, int ldx, const float* R, float* Y, float* hidden, float* tmp, int M,
+// Y = [LayerNorm](act2(relu(X W1^T + b1) W2^T + b2) [+ R]): feed-forward block / two-layer MLP, fused with the hidden rows on chip, else through
+// `hidden` (and `tmp` ahead of a LayerNorm)
+int mlp2(const Plan& p, const Lin& L1, const Lin& L2, const LN* n, const float* X, int ldx, const float* R, float* Y, float* hidden, float* tmp, int M,
          int act2) {
-  if (!tl_free && M >= SMALL_ROWS && L1.N == FF && L2.N == D && L2.K == FF && L1.K <= D && L1.Ws && L2.Ws)
-    return launch_rows(st, X, ldx, M, L1.K, L1.Ws, (size_t)FF * L1.K, L1.b, nullptr, 1, 0, L2.Ws, (size_t)D * L2.K, L2.K, L2.b, act2, R, D,
+  if (!p.free && !p.keep && M >= SMALL_ROWS && L1.N == FF && L2.N == D && L2.K == FF && L1.K <= D && L1.Ws && L2.Ws)
+    return launch_rows(p.st, X, ldx, M, L1.K, L1.Ws, (size_t)FF * L1.K, L1.b, nullptr, 1, 0, L2.Ws, (size_t)D * L2.K, L2.K, L2.b, act2, R, D,
                        n ? n->g : nullptr, n ? n->b : nullptr, Y, D);
-  RC(lin(st, L1, X, ldx, hidden, FF, M, ACT_RELU));
-  if (!n) return lin(st, L2, hidden, FF, Y, D, M, act2, R, D);
-  if (tl_free) {      // (the residual in the GEMM's epilogue, as in proj_ln)
-    RC(lin(st, L2, hidden, FF, tmp, D, M, act2, R, D));
-    return ln(st, tmp, nullptr, *n, Y, M);
+  RC(lin(p, L1, X, ldx, hidden, FF, M, ACT_RELU));
+  if (!n) return lin(p, L2, hidden, FF, Y, D, M, act2, {.R = R, .ldr = D});
+  if (p.free) {      // (the residual in the GEMM's epilogue, as in proj_ln)
+    RC(lin(p, L2, hidden, FF, tmp, D, M, act2, {.R = R, .ldr = D}));
+    return ln(p, tmp, nullptr, *n, Y, M);
   }
-  RC(lin(st, L2, hidden, FF, tmp, D, M, act2));
-  return ln(st, tmp, R, *n, Y, M);
+  RC(lin(p, L2, hidden, FF, tmp, D, M, act2));
+  return ln(p, tmp, R, *n, Y, M);
 }
 
 }  // namespace
@@ -791,48 +827,6 @@ extern "C" size_t glamr_nets_workspace_bytes(const glamr_nets* h, int n_seq, int
 
 namespace {
 
-int encoder_layer(hipStream_t st, const EncLayer& E, Ws& w, float* h_in, float* h_out, int B) {
-  const int M = B * WIN;
-  if (fuse_attention(M)) {
-    const size_t pl = (size_t)3 * D * D;
-    RC(launch_qkv_attention(st, B, QkvAttnArgs{h_in, WIN, h_in, WIN, E.qkv.Ws, pl, E.qkv.b, 0, E.qkv.Ws, pl, E.qkv.b, 8, 16, w.mask, w.att, D}));
-  } else {
-    RC(lin(st, E.qkv, h_in, D, w.qkv, 3 * D, M));
-    launch_attention( dim3(B, 8), dim3(64), 0, st, w.qkv, 3 * D, w.qkv + cp(D), w.qkv + cp(2 * D), 3 * D, w.mask, w.att, D, WIN, WIN, 0);
-  }
-  RC(proj_ln(st, E.o, E.n1, w.att, h_in, h_out, w.tmp, M));
-  RC(mlp2(st, E.f1, E.f2, &E.n2, h_out, D, h_out, h_out, w.ff, w.tmp, M, ACT_NONE));
-  return GLAMR_OK;
-}
-
-// x: [B][Lq][256] queries (in place), ctx keys/values already projected into w.ctxkv ([B][WIN][512]) by the caller
-int decoder_layer(hipStream_t st, const DecLayer& Dl, Ws& w, float* x, const float* ctx, int B, int Lq) {
-  const int M = B * Lq;
-  if (fuse_attention(M)) {
-    const size_t pl = (size_t)3 * D * D;
-    RC(launch_qkv_attention(st, B, QkvAttnArgs{x, Lq, x, Lq, Dl.sa_qkv.Ws, pl, Dl.sa_qkv.b, 0, Dl.sa_qkv.Ws, pl, Dl.sa_qkv.b, 8, 16, nullptr, w.att, D}));
-  } else {
-    RC(lin(st, Dl.sa_qkv, x, D, w.qkv, 3 * D, M));
-    launch_attention( dim3(B, 8), dim3(64), 0, st, w.qkv, 3 * D, w.qkv + cp(D), w.qkv + cp(2 * D), 3 * D, (const unsigned char*)nullptr, w.att, D, Lq, Lq, 0);
-  }
-  RC(proj_ln(st, Dl.sa_o, Dl.n1, w.att, x, x, w.tmp, M));
-  if (fuse_attention(M)) {
-    RC(launch_qkv_attention(st, B, QkvAttnArgs{x, Lq, ctx, WIN, Dl.ca_q.Ws, (size_t)D * D, Dl.ca_q.b, 0, Dl.ca_kv.Ws, (size_t)2 * D * D, Dl.ca_kv.b, 0, 8, w.mask,
-                                               w.att, D}));
-  } else {
-    RC(lin(st, Dl.ca_q, x, D, w.qbuf, D, M));
-    RC(lin(st, Dl.ca_kv, ctx, D, w.ctxkv, 2 * D, B * WIN));
-    launch_attention( dim3(B, 8), dim3(64), 0, st, w.qbuf, D, w.ctxkv, w.ctxkv + cp(D), 2 * D, w.mask, w.att, D, Lq, WIN, 0);
-  }
-  RC(proj_ln(st, Dl.ca_o, Dl.n2, w.att, x, x, w.tmp, M));
-  RC(mlp2(st, Dl.f1, Dl.f2, &Dl.n3, x, D, x, x, w.ff, w.tmp, M, ACT_NONE));
-  return GLAMR_OK;
-}
-
-}  // namespace
-
-namespace {
-
 // ---- kernels of the training-mode / reconstruction passes ---------------------------------------------------------------------
 
 // one 50-frame window handed over as is: rows [B][50][69] -> [B][50][96], key-padding mask = frame not visible
@@ -975,106 +969,147 @@ __global__ __launch_bounds__(256) void traj_to_global2_kernel(const float* raw, 
 }
 
 // ---- one window of the motion infiller --------------------------------------------------------------------------------------------
-// w.x / w.mask hold the window input; on return w.h0 = context [B][50][256], w.z = the latent, w.y = the 30 generated frames [B][30][128].
-// mode 0: z sampled from the prior (eps), 1: from the posterior (needs w.gx = the full window, eps), 2: posterior mode.
-int infiller_window(glamr_nets* h, hipStream_t st, Ws& w, int B, int mode, const float* eps, int eps_stride, float* q_out, float* p_out) {
+// The forward below is the ONLY launch sequence of the window: the workspace path (window_slots: aliased slots, fused kernels from SMALL_ROWS rows
+// on, which leave the slots they skip unwritten) and the taped path (a keep plan on distinct slots) both run it.
+// e.out = layer(h_in) over the window's 50 rows per sequence
+int encoder_layer(const Plan& p, const EncLayer& E, const EncTape& e, const unsigned char* mask, const float* h_in, int B) {
   const int M = B * WIN;
-  RC(lin(st, h->enc_in, w.x, XLD, w.h0, D, M, ACT_NONE, nullptr, 0, h->enc_pe, -WIN, D, 0));      // (w.x is row-major in every mode)      // + the position table, in the GEMM's epilogue
-  RC(encoder_layer(st, h->enc[0], w, w.h0, w.h1, B));
-  RC(encoder_layer(st, h->enc[1], w, w.h1, w.h0, B));
-  float* ctx = w.h0;
+  if (fuse_attention(p, M)) {
+    const size_t pl = (size_t)3 * D * D;
+    RC(launch_qkv_attention(p.st, B, QkvAttnArgs{h_in, WIN, h_in, WIN, E.qkv.Ws, pl, E.qkv.b, 0, E.qkv.Ws, pl, E.qkv.b, 8, 16, mask, e.att, D}));
+  } else {
+    RC(lin(p, E.qkv, h_in, D, e.qkv, 3 * D, M));
+    launch_attention(p, B, e.qkv, 3 * D, e.qkv + p.cp(D), e.qkv + p.cp(2 * D), 3 * D, mask, e.att, D, WIN, WIN, 0);
+  }
+  RC(proj_ln(p, E.o, E.n1, e.att, h_in, e.mid, e.tmp1, M));
+  return mlp2(p, E.f1, E.f2, &E.n2, e.mid, D, e.mid, e.out, e.ff, e.tmp2, M, ACT_NONE);
+}
+// d.xc = layer(x) for [B][Lq][256] queries x attending to each other and to the context rows ctx [B][WIN][256]
+int decoder_layer(const Plan& p, const DecLayer& Dl, const DecTape& d, const unsigned char* mask, const float* x, const float* ctx, int B, int Lq) {
+  const int M = B * Lq;
+  if (fuse_attention(p, M)) {
+    const size_t pl = (size_t)3 * D * D;
+    RC(launch_qkv_attention(p.st, B, QkvAttnArgs{x, Lq, x, Lq, Dl.sa_qkv.Ws, pl, Dl.sa_qkv.b, 0, Dl.sa_qkv.Ws, pl, Dl.sa_qkv.b, 8, 16, nullptr, d.att_s, D}));
+  } else {
+    RC(lin(p, Dl.sa_qkv, x, D, d.qkv, 3 * D, M));
+    launch_attention(p, B, d.qkv, 3 * D, d.qkv + p.cp(D), d.qkv + p.cp(2 * D), 3 * D, nullptr, d.att_s, D, Lq, Lq, 0);
+  }
+  RC(proj_ln(p, Dl.sa_o, Dl.n1, d.att_s, x, d.xa, d.tmp_s, M));
+  if (fuse_attention(p, M)) {
+    RC(launch_qkv_attention(p.st, B, QkvAttnArgs{d.xa, Lq, ctx, WIN, Dl.ca_q.Ws, (size_t)D * D, Dl.ca_q.b, 0, Dl.ca_kv.Ws, (size_t)2 * D * D, Dl.ca_kv.b, 0, 8, mask,
+                                                 d.att_c, D}));
+  } else {
+    RC(lin(p, Dl.ca_q, d.xa, D, d.qbuf, D, M));
+    RC(lin(p, Dl.ca_kv, ctx, D, d.ctxkv, 2 * D, B * WIN));
+    launch_attention(p, B, d.qbuf, D, d.ctxkv, d.ctxkv + p.cp(D), 2 * D, mask, d.att_c, D, Lq, WIN, 0);
+  }
+  RC(proj_ln(p, Dl.ca_o, Dl.n2, d.att_c, d.xa, d.xb, d.tmp_c, M));
+  return mlp2(p, Dl.f1, Dl.f2, &Dl.n3, d.xb, D, d.xb, d.xc, d.ff, d.tmp_f, M, ACT_NONE);
+}
+
+// w.x / w.mask hold the window input; on return w.enc[1].out = context [B][50][256], w.z = the latent, w.y = the 30 generated frames [B][30][128].
+// mode 0: z sampled from the prior (eps), 1: from the posterior (needs w.gx = the full window, eps), 2: posterior mode.
+int infiller_window(glamr_nets* h, const Plan& p, const WinTape& w, int B, int mode, const float* eps, int eps_stride, float* q_out, float* p_out) {
+  const int M = B * WIN, MC = B * CUR;
+  hipStream_t st = p.st;
+  // + the position table, in the GEMM's epilogue (w.x is row-major under every plan)
+  RC(lin(p, h->enc_in, w.x, XLD, w.h0, D, M, ACT_NONE, {.rowbias = h->enc_pe, .rpg = -WIN, .ldrb = D, .x_rowmajor = true}));
+  RC(encoder_layer(p, h->enc[0], w.enc[0], w.mask, w.h0, B));
+  RC(encoder_layer(p, h->enc[1], w.enc[1], w.mask, w.enc[0].out, B));
+  const float* ctx = w.enc[1].out;
   if (mode != GLAMR_VAE_INFER) {
-    // posterior: [mu token, logvar token, 30 current frames] attend to each other and to the context (DataEncoder.forward :204-249)
-    float* x32 = w.dq;
-    hipLaunchKernelGGL(posterior_rows_kernel, dim3(B, 32), dim3(XLD), 0, st, w.gx, w.h1);      // w.h1 is free after the encoder: [B][32][96] rows
-    RC(lin(st, h->qe_in, w.h1, XLD, x32, D, B * 32, ACT_NONE, nullptr, 0, h->qe_table, -32, D));
-    RC(decoder_layer(st, h->qe[0], w, x32, ctx, B, 32));
-    RC(decoder_layer(st, h->qe[1], w, x32, ctx, B, 32));
-    hipLaunchKernelGGL(take_rows_kernel, dim3(B, 2), dim3(D), 0, st, x32, 32, 2, w.q2);
-    RC(lin(st, h->qe_pz, w.q2, D, w.qpz, D, B * 2));
+    // posterior: [mu token, logvar token, 30 current frames] attend to each other and to the context (DataEncoder.forward :204-249), on
+    // the decoder's slots ahead of the decoder
+    float* rows32 = w.enc[0].out;      // free after the encoder: [B][32][96] rows
+    hipLaunchKernelGGL(posterior_rows_kernel, dim3(B, 32), dim3(XLD), 0, st, w.gx, rows32);
+    RC(lin(p, h->qe_in, rows32, XLD, w.q0, D, B * 32, ACT_NONE, {.rowbias = h->qe_table, .rpg = -32, .ldrb = D}));
+    RC(decoder_layer(p, h->qe[0], w.dec[0], w.mask, w.q0, ctx, B, 32));
+    RC(decoder_layer(p, h->qe[1], w.dec[1], w.mask, w.dec[0].xc, ctx, B, 32));
+    hipLaunchKernelGGL(take_rows_kernel, dim3(B, 2), dim3(D), 0, st, w.dec[1].xc, 32, 2, w.q2);
+    RC(lin(p, h->qe_pz, w.q2, D, w.qpz, D, B * 2));
     if (q_out) hipLaunchKernelGGL(dist_out_kernel, dim3(B), dim3(NZ), 0, st, w.qpz, q_out);
   }
   // prior: two learned tokens attend to the context
-  RC(lin(st, h->prior_kv, ctx, D, w.ctxkv, 2 * D, M));
-  launch_attention( dim3(B, 8), dim3(64), 0, st, h->prior_q, D, w.ctxkv, w.ctxkv + cp(D), 2 * D, w.mask, w.att, D, 2, WIN, 1);
-  RC(lin(st, h->prior_o, w.att, D, w.tmp, D, B * 2));
-  hipLaunchKernelGGL(tile_rows_kernel, dim3((B * 2 * D + 255) / 256), dim3(64), 0, st, w.dq, h->prior_x1, 2, B * 2 * D, tl_free);
-  RC(ln(st, w.tmp, w.dq, h->prior_n2, w.dq, B * 2));
-  RC(lin(st, h->prior_f1, w.dq, D, w.ff, FF, B * 2, ACT_RELU));
-  RC(lin(st, h->prior_f2, w.ff, FF, w.tmp, D, B * 2));
-  RC(ln(st, w.tmp, w.dq, h->prior_n3, w.dq, B * 2));
-  RC(lin(st, h->prior_pz, w.dq, D, w.pz, D, B * 2, ACT_NONE, nullptr, 0, nullptr, 1, 0, -1, 0));      // row-major out: elementwise kernels read it
+  RC(lin(p, h->prior_kv, ctx, D, w.p_ctxkv, 2 * D, M));
+  launch_attention(p, B, h->prior_q, D, w.p_ctxkv, w.p_ctxkv + p.cp(D), 2 * D, w.mask, w.p_att, D, 2, WIN, 1);
+  RC(lin(p, h->prior_o, w.p_att, D, w.p_tmp1, D, B * 2));
+  hipLaunchKernelGGL(tile_rows_kernel, dim3((B * 2 * D + 255) / 256), dim3(64), 0, st, w.p_x1, h->prior_x1, 2, B * 2 * D, (int)p.free);
+  RC(ln(p, w.p_tmp1, w.p_x1, h->prior_n2, w.p_a, B * 2));
+  RC(lin(p, h->prior_f1, w.p_a, D, w.p_ff, FF, B * 2, ACT_RELU));
+  RC(lin(p, h->prior_f2, w.p_ff, FF, w.p_tmp2, D, B * 2));
+  RC(ln(p, w.p_tmp2, w.p_a, h->prior_n3, w.p_b, B * 2));
+  RC(lin(p, h->prior_pz, w.p_b, D, w.pz, D, B * 2, ACT_NONE, {.y_rowmajor = true}));      // row-major out: elementwise kernels read it
   if (p_out) hipLaunchKernelGGL(dist_out_kernel, dim3(B), dim3(NZ), 0, st, w.pz, p_out);
   if (mode == GLAMR_VAE_INFER) hipLaunchKernelGGL(reparam_infiller_kernel, dim3(B), dim3(64), 0, st, w.pz, eps, eps_stride, w.z, B);
   else if (mode == GLAMR_VAE_TRAIN) hipLaunchKernelGGL(reparam_infiller_kernel, dim3(B), dim3(64), 0, st, w.qpz, eps, eps_stride, w.z, B);
   else hipLaunchKernelGGL(mode_infiller_kernel, dim3(B), dim3(NZ), 0, st, w.qpz, w.z);
   // decoder: 30 queries = position code of z
-  RC(lin(st, h->dec_z, w.z, NZ, w.zproj, D, B, ACT_NONE, nullptr, 0, nullptr, 1, 0, 0, 0));
-  hipLaunchKernelGGL(build_queries_kernel, dim3(B, CUR), dim3(64), 0, st, w.zproj, h->dec_pe, w.dq, tl_free);
-  RC(decoder_layer(st, h->dec[0], w, w.dq, ctx, B, CUR));
-  RC(decoder_layer(st, h->dec[1], w, w.dq, ctx, B, CUR));
-  RC(mlp2(st, h->out1, h->out2, nullptr, w.dq, D, nullptr, w.tmp, w.ff, w.tmp, B * CUR, ACT_RELU));
-  RC(lin(st, h->outfc, w.tmp, D, w.y, 128, B * CUR, ACT_NONE, nullptr, 0, nullptr, 1, 0, -1, 0));
-  return GLAMR_OK;
+  RC(lin(p, h->dec_z, w.z, NZ, w.zproj, D, B, ACT_NONE, {.x_rowmajor = true, .y_rowmajor = true}));
+  hipLaunchKernelGGL(build_queries_kernel, dim3(B, CUR), dim3(64), 0, st, w.zproj, h->dec_pe, w.q0, (int)p.free);
+  RC(decoder_layer(p, h->dec[0], w.dec[0], w.mask, w.q0, ctx, B, CUR));
+  RC(decoder_layer(p, h->dec[1], w.dec[1], w.mask, w.dec[0].xc, ctx, B, CUR));
+  RC(mlp2(p, h->out1, h->out2, nullptr, w.dec[1].xc, D, nullptr, w.o2, w.o1, nullptr, MC, ACT_RELU));
+  return lin(p, h->outfc, w.o2, D, w.y, 128, MC, ACT_NONE, {.y_rowmajor = true});
 }
 
 #include "nets_tape.hpp"
 
-void bilstm(glamr_nets* h, hipStream_t st, const float* G, float* const hh[2], const int* lens, float* H, int max_len, int B) {
+void bilstm(const Plan& p, const float* G, float* const hh[2], const int* lens, float* H, int max_len, int B) {
   LstmArgs la{G, hh[0], hh[1], lens, H, max_len};
   // large batches: 16 sequences per workgroup on the matrix cores; small ones: one sequence per workgroup keeps every CU busy
-  if (B >= 512 && !tl_fp32) hipLaunchKernelGGL(lstm_mfma_kernel, dim3((B + 15) / 16, 2), dim3(512), 0, st, la, B);
-  else hipLaunchKernelGGL(lstm_kernel, dim3(B, 2), dim3(512), 0, st, la);
+  if (B >= 512 && !p.fp32) hipLaunchKernelGGL(lstm_mfma_kernel, dim3((B + 15) / 16, 2), dim3(512), 0, p.st, la, B);
+  else hipLaunchKernelGGL(lstm_kernel, dim3(B, 2), dim3(512), 0, p.st, la);
 }
 
 // ---- the trajectory predictor on joint rows w.tx [B][max_len][96] -------------------------------------------------------------------
 // lens_run: frames the recurrent layers and the temporal means cover.  mode as above; modes 1 / 2 need w.e6 (encoder rows) and use
 // `init` (first row of the ground-truth local trajectory) for the first output row.
-int traj_pass(glamr_nets* h, hipStream_t st, Ws& w, int B, int max_len, const int* lens_run, int mode, const float* eps, float* q_out, float* p_out,
+int traj_pass(glamr_nets* h, const Plan& p, Ws& w, int B, int max_len, const int* lens_run, int mode, const float* eps, float* q_out, float* p_out,
               const float* init, int ldinit, float* out_orig, float* out_local, float* out_trans, float* out_orient, float* out_orient_q) {
   const int MT = B * max_len;
-  RC(mlp2(st, h->t_in1, h->t_in2, nullptr, w.tx, XLD, nullptr, w.th, w.tg, w.tq, MT, ACT_RELU));
+  hipStream_t st = p.st;
+  RC(mlp2(p, h->t_in1, h->t_in2, nullptr, w.tx, XLD, nullptr, w.th, w.tg, w.tq, MT, ACT_RELU));
   for (int l = 0; l < 2; ++l) {
-    RC(lin(st, h->t_ih[l], w.th, D, w.tg, 1024, MT));
-    bilstm(h, st, w.tg, h->t_hh[l], lens_run, w.th, max_len, B);
+    RC(lin(p, h->t_ih[l], w.th, D, w.tg, 1024, MT));
+    bilstm(p, w.tg, h->t_hh[l], lens_run, w.th, max_len, B);
   }
-  RC(mlp2(st, h->t_out1, h->t_out2, nullptr, w.th, D, nullptr, w.th, w.tg, w.tq, MT, ACT_RELU));       // context [B][max_len][256]
+  RC(mlp2(p, h->t_out1, h->t_out2, nullptr, w.th, D, nullptr, w.th, w.tg, w.tq, MT, ACT_RELU));       // context [B][max_len][256]
   if (mode != GLAMR_VAE_INFER) {
     // posterior (DataEncoder.forward :160-199): [t_h, aa(q_h)] -> in_mlp -> 2 bi-LSTM -> out_mlp; fused with the context, mean over time
-    RC(lin(st, h->te_in1, w.e6, 32, w.tg, FF, MT, ACT_RELU));
-    RC(lin(st, h->te_in2, w.tg, FF, w.te, D, MT, ACT_RELU));
+    RC(lin(p, h->te_in1, w.e6, 32, w.tg, FF, MT, ACT_RELU));
+    RC(lin(p, h->te_in2, w.tg, FF, w.te, D, MT, ACT_RELU));
     for (int l = 0; l < 2; ++l) {
-      RC(lin(st, h->te_ih[l], w.te, D, w.tg, 1024, MT));
-      bilstm(h, st, w.tg, h->te_hh[l], lens_run, w.te, max_len, B);
+      RC(lin(p, h->te_ih[l], w.te, D, w.tg, 1024, MT));
+      bilstm(p, w.tg, h->te_hh[l], lens_run, w.te, max_len, B);
     }
-    RC(lin(st, h->te_out1, w.te, D, w.tg, FF, MT, ACT_RELU));
-    RC(lin(st, h->te_out2, w.tg, FF, w.tcat, FF, MT, ACT_RELU));     // columns [0,256) of the fused rows
+    RC(lin(p, h->te_out1, w.te, D, w.tg, FF, MT, ACT_RELU));
+    RC(lin(p, h->te_out2, w.tg, FF, w.tcat, FF, MT, ACT_RELU));     // columns [0,256) of the fused rows
     hipLaunchKernelGGL(copy_cols_kernel, dim3(((size_t)MT * D + 255) / 256), dim3(256), 0, st, w.th, D, w.tcat, FF, D, (size_t)MT * D);
-    RC(lin(st, h->te_f1, w.tcat, FF, w.tg, FF, MT, ACT_RELU));
-    RC(lin(st, h->te_f2, w.tg, FF, w.te, D, MT, ACT_RELU));
+    RC(lin(p, h->te_f1, w.tcat, FF, w.tg, FF, MT, ACT_RELU));
+    RC(lin(p, h->te_f2, w.tg, FF, w.te, D, MT, ACT_RELU));
     hipLaunchKernelGGL(masked_mean_kernel, dim3(B, 4), dim3(64), 0, st, w.te, max_len, lens_run, w.tmean);
-    RC(lin(st, h->te_qz, w.tmean, D, w.tqz, D, B));
+    RC(lin(p, h->te_qz, w.tmean, D, w.tqz, D, B));
     if (q_out) GLAMR_HIP_CHECK(hipMemcpyAsync(q_out, w.tqz, (size_t)B * D * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
   hipLaunchKernelGGL(masked_mean_kernel, dim3(B, 4), dim3(64), 0, st, w.th, max_len, lens_run, w.tmean);
-  RC(lin(st, h->t_pr1, w.tmean, D, w.trow, FF, B, ACT_RELU));
-  RC(lin(st, h->t_pr2, w.trow, FF, w.tmean, D, B, ACT_RELU));
-  RC(lin(st, h->t_pz, w.tmean, D, w.pz, D, B));
+  RC(lin(p, h->t_pr1, w.tmean, D, w.trow, FF, B, ACT_RELU));
+  RC(lin(p, h->t_pr2, w.trow, FF, w.tmean, D, B, ACT_RELU));
+  RC(lin(p, h->t_pz, w.tmean, D, w.pz, D, B));
   if (p_out) GLAMR_HIP_CHECK(hipMemcpyAsync(p_out, w.pz, (size_t)B * D * sizeof(float), hipMemcpyDeviceToDevice, st));
   if (mode == GLAMR_VAE_INFER) hipLaunchKernelGGL(reparam_traj_kernel, dim3(B), dim3(64), 0, st, w.pz, eps, w.z);
   else if (mode == GLAMR_VAE_TRAIN) hipLaunchKernelGGL(reparam_traj_kernel, dim3(B), dim3(64), 0, st, w.tqz, eps, w.z);
   else hipLaunchKernelGGL(mode_traj_kernel, dim3(B), dim3(NZ), 0, st, w.tqz, w.z);
-  RC(lin(st, h->t_dz, w.z, NZ, w.trow, FF, B));      // W_z z + b, one row per sequence
+  RC(lin(p, h->t_dz, w.z, NZ, w.trow, FF, B));      // W_z z + b, one row per sequence
   // decoder MLP: relu(W_ctx ctx + [W_z z + b] of the sequence) -> relu(W_2 .): as ONE row-block launch (the 512-wide hidden rows stay in LDS:
   // 629 MB less written and read again per 1024 x 300 frames)
-  if (!tl_fp32 && MT >= SMALL_ROWS && max_len >= 64 && h->t_dctx.Ws && h->t_d2.Ws && h->t_dctx.K == D && h->t_dctx.N == FF && h->t_d2.K == FF && h->t_d2.N == D) {
+  if (!p.fp32 && MT >= SMALL_ROWS && max_len >= 64 && h->t_dctx.Ws && h->t_d2.Ws && h->t_dctx.K == D && h->t_dctx.N == FF && h->t_d2.K == FF && h->t_d2.N == D) {
     RC(launch_rows(st, w.th, D, MT, D, h->t_dctx.Ws, (size_t)FF * D, h->t_dctx.b, w.trow, max_len, FF, h->t_d2.Ws, (size_t)D * FF, FF, h->t_d2.b, ACT_RELU,
                    nullptr, D, nullptr, nullptr, w.tq, D));
   } else {
-    RC(lin(st, h->t_dctx, w.th, D, w.tg, FF, MT, ACT_RELU, nullptr, 0, w.trow, max_len, FF));
-    RC(lin(st, h->t_d2, w.tg, FF, w.tq, D, MT, ACT_RELU));
+    RC(lin(p, h->t_dctx, w.th, D, w.tg, FF, MT, ACT_RELU, {.rowbias = w.trow, .rpg = max_len, .ldrb = FF}));
+    RC(lin(p, h->t_d2, w.tg, FF, w.tq, D, MT, ACT_RELU));
   }
-  RC(lin(st, h->t_dfc, w.tq, D, w.traw, 64, MT));
+  RC(lin(p, h->t_dfc, w.tq, D, w.traw, 64, MT));
   if (out_orig) hipLaunchKernelGGL(rows_out_kernel, dim3(MT), dim3(64), 0, st, w.traw, 64, MT, 11, out_orig);
   hipLaunchKernelGGL(traj_to_global2_kernel, dim3(B), dim3(256), 0, st, w.traw, 64, max_len, lens_run, init, ldinit, 1, out_local, out_trans, out_orient,
                      out_orient_q, w.tscr);
@@ -1084,16 +1119,54 @@ int traj_pass(glamr_nets* h, hipStream_t st, Ws& w, int B, int max_len, const in
 }  // namespace
 
 namespace {
+// validates the lengths of a batch; *n_win = windows its longest sequence needs
+int count_windows(const int32_t* lens_host, int B, int max_len, int* n_win) {
+  int longest = 0;
+  for (int b = 0; b < B; ++b) {
+    GLAMR_REQUIRE(lens_host[b] > PAST && lens_host[b] <= max_len, "sequence %d has length %d (need %d < len <= max_len)", b, lens_host[b], PAST);
+    longest = std::max(longest, (int)lens_host[b]);
+  }
+  *n_win = windows_of(longest);
+  return GLAMR_OK;
+}
+
+// Uploads the lengths of a call to lens_dev; *capturing = a caller is CAPTURING this stream (its whole step, or its iteration of the
+// latent-optimisation mode, as one graph).  Such a caller gets the upload recorded into its graph: the lengths are copied to a pinned table
+// the handle owns (alive until glamr_nets_destroy) and the graph reads that table at every replay -- a copy node must not read pageable memory
+// that is gone by then, and the caller's graph is self-contained whatever workspace it was captured with.  kernel_copy: under capture the
+// upload is a KERNEL reading the pinned table (hipHostMalloc memory is device-visible) instead of a copy node.  (Round 5 blamed copy nodes at
+// the start of a graph for the two-stream corruption; round 6 found the cause elsewhere -- packed-fp32 instructions, glamr_amd/build.py --
+// and a copy node replays bit-identically: profiles/r06_pipeline_corruption.log.)
+int stage_lens(glamr_nets* h, hipStream_t st, const int32_t* lens_host, int B, int* lens_dev, bool kernel_copy, bool* capturing) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  *capturing = st != nullptr && hipStreamIsCapturing(st, &cap) == hipSuccess && cap == hipStreamCaptureStatusActive;
+  const int32_t* lens_src = lens_host;
+  if (*capturing) {
+    std::lock_guard<std::mutex> lock(h->graph_mu);
+    GLAMR_REQUIRE(h->capture_lens && h->capture_lens_used + (size_t)B <= CAPTURE_LENS_INTS,
+                  "the handle's table for calls recorded into caller graphs is full (%zu lengths); destroy and re-create the handle", CAPTURE_LENS_INTS);
+    int32_t* pinned = h->capture_lens + h->capture_lens_used;
+    h->capture_lens_used += (size_t)B;
+    std::memcpy(pinned, lens_host, (size_t)B * sizeof(int32_t));
+    lens_src = pinned;
+  }
+  if (*capturing && kernel_copy) hipLaunchKernelGGL(copy_ints_kernel, dim3((B + 255) / 256), dim3(256), 0, st, lens_dev, lens_src, B);
+  else GLAMR_HIP_CHECK(hipMemcpyAsync(lens_dev, lens_src, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
+  return GLAMR_OK;
+}
+
 // the launch sequence of glamr_nets_infer (w.lens already holds the lengths)
-int enqueue_infer(glamr_nets* h, hipStream_t st, Ws& w, int B, int max_len, int n_win, int n_win_max, bool do_infill, bool do_traj, const float* body_pose,
+int enqueue_infer(glamr_nets* h, const Plan& p, Ws& w, int B, int max_len, int n_win, int n_win_max, bool do_infill, bool do_traj, const float* body_pose,
                   const float* visible, const float* motion_eps, const float* traj_eps, float* out_pose, float* out_local_traj, float* out_trans,
                   float* out_orient) {
+  hipStream_t st = p.st;
+  const WinTape win = window_slots(w);
   hipLaunchKernelGGL(pose_in_kernel, dim3(B, w.Tpad), dim3(64), 0, st, body_pose, max_len, w.Tpad, w.pose);
   // ---- motion infiller: autoregressive windows [30 i, 30 i + 50) ------------------------------------------------------------
   for (int i = 0; do_infill && i < n_win; ++i) {
     const int s = i * CUR;
     hipLaunchKernelGGL(window_gather_kernel, dim3(B, WIN), dim3(64), 0, st, w.pose, visible, w.lens, w.Tpad, max_len, s, w.x, w.mask);
-    RC(infiller_window(h, st, w, B, GLAMR_VAE_INFER, motion_eps + (size_t)i * NZ, n_win_max * NZ, nullptr, nullptr));
+    RC(infiller_window(h, p, win, B, GLAMR_VAE_INFER, motion_eps + (size_t)i * NZ, n_win_max * NZ, nullptr, nullptr));
     hipLaunchKernelGGL(window_scatter_kernel, dim3(B, CUR), dim3(64), 0, st, w.y, 128, w.lens, w.Tpad, s, w.pose);
   }
   if (out_pose) hipLaunchKernelGGL(pose_out_kernel, dim3(B, max_len), dim3(64), 0, st, w.pose, max_len, w.Tpad, w.lens, out_pose);
@@ -1103,10 +1176,10 @@ int enqueue_infer(glamr_nets* h, hipStream_t st, Ws& w, int B, int max_len, int 
   // projection: 1.9 ms on the LDS-free kernels, 1.2 on these).  Rounds 3 - 4 kept that prefix co-schedulable to use the slack beside the other
   // stream's stage; with the stage launch (27 ms beside the priors) now shorter than the infiller beside it (29 ms) the prefix starts when the
   // stage has just retired and finds an empty GPU: 37.9 -> 37.2 ms per step, alternated twice on one box (profiles/r05_pipeline_experiments.log).
-  struct Restore { int v; ~Restore() { tl_free = v; } } restore{tl_free};      // (a second enqueue after a failed capture starts from the same mode)
-  tl_free = 0;
+  Plan tp = p;
+  tp.free = false;
   hipLaunchKernelGGL(fk_joints_kernel, dim3(B, (max_len + FK_FRAMES - 1) / FK_FRAMES), dim3(256), 0, st, w.pose, w.Tpad, max_len, w.lens, h->rest_joints, h->parents, w.tx);
-  return traj_pass(h, st, w, B, max_len, w.lens, GLAMR_VAE_INFER, traj_eps, nullptr, nullptr, nullptr, 0, nullptr, out_local_traj, out_trans, out_orient, nullptr);
+  return traj_pass(h, tp, w, B, max_len, w.lens, GLAMR_VAE_INFER, traj_eps, nullptr, nullptr, nullptr, 0, nullptr, out_local_traj, out_trans, out_orient, nullptr);
 }
 }  // namespace
 
@@ -1118,39 +1191,19 @@ extern "C" int glamr_nets_infer(glamr_nets* h, int B, int max_len, const int32_t
   GLAMR_REQUIRE(!do_infill || (visible && motion_eps && out_pose), "infilling needs visible, motion_eps and out_pose");
   GLAMR_REQUIRE(!do_traj || (traj_eps && out_local_traj && out_trans && out_orient), "trajectory prediction needs traj_eps and its three outputs");
   GLAMR_REQUIRE(B > 0 && max_len > PAST, "need n_seq > 0 and max_len > %d", PAST);
-  int longest = 0;
-  for (int b = 0; b < B; ++b) {
-    GLAMR_REQUIRE(lens_host[b] > PAST && lens_host[b] <= max_len, "sequence %d has length %d (need %d < len <= max_len)", b, lens_host[b], PAST);
-    longest = std::max(longest, (int)lens_host[b]);
-  }
-  const int n_win = (longest - PAST + CUR - 1) / CUR;
+  int n_win = 0;
+  RC(count_windows(lens_host, B, max_len, &n_win));
   GLAMR_REQUIRE(!do_infill || n_win <= n_win_max, "motion_eps holds %d windows per sequence, %d needed", n_win_max, n_win);
   hipStream_t st = static_cast<hipStream_t>(stream_);
-  tl_fp32 = h->fp32_only ? 1 : 0;
-  tl_free = (!tl_fp32 && free_wanted(flags) && (size_t)B * WIN >= (size_t)SMALL_ROWS) ? 1 : 0;
+  // the co-schedulable kernels from SMALL_ROWS window rows on (below it a sequence alone and inside a small batch agree to the bit, nn_kernels.hpp)
+  const bool fp32 = h->fp32_only;
+  const Plan plan{st, fp32, !fp32 && free_wanted(flags) && (size_t)B * WIN >= (size_t)SMALL_ROWS, false};
   Ws w = ws_layout(B, max_len, static_cast<char*>(workspace));
-  // A caller that is CAPTURING this stream (its whole step as one graph) gets the plain launch sequence recorded into its graph,
-  // INCLUDING the upload of the lengths: they are copied to a pinned table the handle owns (alive until glamr_nets_destroy), and the
-  // copy node reads that table at every replay -- the caller's graph is self-contained whatever workspace it was captured with.
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  const bool outer_capture = st != nullptr && hipStreamIsCapturing(st, &cap) == hipSuccess && cap == hipStreamCaptureStatusActive;
-  const int32_t* lens_src = lens_host;
-  if (outer_capture) {
-    std::lock_guard<std::mutex> lock(h->graph_mu);
-    GLAMR_REQUIRE(h->capture_lens && h->capture_lens_used + (size_t)B <= CAPTURE_LENS_INTS,
-                  "the handle's table for calls recorded into caller graphs is full (%zu lengths); destroy and re-create the handle", CAPTURE_LENS_INTS);
-    int32_t* pinned = h->capture_lens + h->capture_lens_used;
-    h->capture_lens_used += (size_t)B;
-    std::memcpy(pinned, lens_host, (size_t)B * sizeof(int32_t));
-    lens_src = pinned;
-  }
-  // Recorded into a caller's graph the upload is a KERNEL reading the pinned table (hipHostMalloc memory is device-visible).  (Round 5 blamed
-  // copy nodes at the start of a graph for the two-stream corruption; round 6 found the cause elsewhere -- packed-fp32 instructions,
-  // glamr_amd/build.py -- and a copy node replays bit-identically: profiles/r06_pipeline_corruption.log.)
-  if (outer_capture) hipLaunchKernelGGL(copy_ints_kernel, dim3((B + 255) / 256), dim3(256), 0, st, w.lens, lens_src, B);
-  else GLAMR_HIP_CHECK(hipMemcpyAsync(w.lens, lens_src, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
+  // (a capturing caller gets the plain launch sequence below recorded into its graph, the upload of the lengths included)
+  bool outer_capture = false;
+  RC(stage_lens(h, st, lens_host, B, w.lens, true, &outer_capture));
   auto enqueue = [&]() -> int {
-    return enqueue_infer(h, st, w, B, max_len, n_win, n_win_max, do_infill, do_traj, body_pose, visible, motion_eps, traj_eps, out_pose, out_local_traj, out_trans,
+    return enqueue_infer(h, plan, w, B, max_len, n_win, n_win_max, do_infill, do_traj, body_pose, visible, motion_eps, traj_eps, out_pose, out_local_traj, out_trans,
                          out_orient);
   };
   // A batch is ~450 kernel launches.  The same call (same geometry, same buffers -- a caching allocator hands the same blocks back in
@@ -1159,7 +1212,7 @@ extern "C" int glamr_nets_infer(glamr_nets* h, int B, int max_len, const int32_t
   if (!outer_capture) {
     glamr_nets::GraphKey key;
     std::memset(&key, 0, sizeof(key));
-    key.v[0] = B; key.v[1] = max_len; key.v[2] = n_win; key.v[3] = flags | (tl_free << 16); key.v[4] = n_win_max;
+    key.v[0] = B; key.v[1] = max_len; key.v[2] = n_win; key.v[3] = flags | ((int)plan.free << 16); key.v[4] = n_win_max;
     const void* ptrs[9] = {body_pose, visible, motion_eps, traj_eps, out_pose, out_local_traj, out_trans, out_orient, workspace};
     for (int i = 0; i < 9; ++i) key.p[i] = ptrs[i];
     std::lock_guard<std::mutex> lock(h->graph_mu);
@@ -1214,13 +1267,13 @@ extern "C" int glamr_nets_infiller_window(glamr_nets* h, int B, int mode, const 
   GLAMR_REQUIRE(mode == GLAMR_VAE_INFER || io->body_pose, "the posterior encoder (train / recon) needs body_pose");
   GLAMR_REQUIRE(mode == GLAMR_VAE_RECON || io->eps, "sampling (infer / train) needs eps");
   hipStream_t st = static_cast<hipStream_t>(stream_);
-  tl_fp32 = h->fp32_only ? 1 : 0;
-  tl_free = 0;
+  const Plan plan{st, h->fp32_only, false, false};
   Ws w = ws_layout(B, WIN, static_cast<char*>(workspace));
+  const WinTape win = window_slots(w);
   hipLaunchKernelGGL(window_in_kernel, dim3(B, WIN), dim3(XLD), 0, st, io->in_body_pose, io->frame_mask, w.x, w.mask);
   if (mode != GLAMR_VAE_INFER) hipLaunchKernelGGL(window_in_kernel, dim3(B, WIN), dim3(XLD), 0, st, io->body_pose, io->frame_mask, w.gx, (unsigned char*)nullptr);
-  RC(infiller_window(h, st, w, B, mode, io->eps, NZ, io->q_z, io->p_z));
-  if (io->context) GLAMR_HIP_CHECK(hipMemcpyAsync(io->context, w.h0, (size_t)B * WIN * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+  RC(infiller_window(h, plan, win, B, mode, io->eps, NZ, io->q_z, io->p_z));
+  if (io->context) GLAMR_HIP_CHECK(hipMemcpyAsync(io->context, win.enc[1].out, (size_t)B * WIN * D * sizeof(float), hipMemcpyDeviceToDevice, st));
   if (io->z) GLAMR_HIP_CHECK(hipMemcpyAsync(io->z, w.z, (size_t)B * NZ * sizeof(float), hipMemcpyDeviceToDevice, st));
   hipLaunchKernelGGL(rows_out_kernel, dim3(B * CUR), dim3(128), 0, st, w.y, 128, B * CUR, 69, io->out_body_pose);
   GLAMR_HIP_CHECK(hipGetLastError());
@@ -1235,8 +1288,7 @@ extern "C" int glamr_nets_traj_clip(glamr_nets* h, int B, int T, int mode, const
   GLAMR_REQUIRE(mode == GLAMR_VAE_RECON || io->eps, "sampling (infer / train) needs eps");
   GLAMR_REQUIRE(io->out_local_traj, "out_local_traj is required");
   hipStream_t st = static_cast<hipStream_t>(stream_);
-  tl_fp32 = h->fp32_only ? 1 : 0;
-  tl_free = 0;
+  const Plan plan{st, h->fp32_only, false, false};
   Ws w = ws_layout(B, T, static_cast<char*>(workspace));
   std::vector<int> run(B, T), valid(B, T);
   if (io->valid_len > 0 && io->valid_len < T) std::fill(valid.begin(), valid.end(), io->valid_len);      // zero-padded chunk (get_seg_data)
@@ -1256,7 +1308,7 @@ extern "C" int glamr_nets_traj_clip(glamr_nets* h, int B, int T, int mode, const
   }
   int ldinit = T * 11;
   if (io->init_row) { init = io->init_row; ldinit = 11; }      // :319-321 takes precedence
-  RC(traj_pass(h, st, w, B, T, w.lens, mode, io->eps, io->q_z, io->p_z, init, ldinit, io->out_orig_local_traj, io->out_local_traj, io->out_trans,
+  RC(traj_pass(h, plan, w, B, T, w.lens, mode, io->eps, io->q_z, io->p_z, init, ldinit, io->out_orig_local_traj, io->out_local_traj, io->out_trans,
                io->out_orient, io->out_orient_q));
   if (io->z) GLAMR_HIP_CHECK(hipMemcpyAsync(io->z, w.z, (size_t)B * NZ * sizeof(float), hipMemcpyDeviceToDevice, st));
   GLAMR_HIP_CHECK(hipStreamSynchronize(st));          // `run` / `valid` are pageable host buffers
@@ -1292,51 +1344,24 @@ extern "C" size_t glamr_nets_tape_bytes(const glamr_nets* h, int n_seq, int max_
   return tape_layout(n_seq, max_len, nullptr).total;
 }
 
-namespace {
-int tape_windows(const int32_t* lens_host, int B, int max_len, int* n_win) {
-  int longest = 0;
-  for (int b = 0; b < B; ++b) {
-    GLAMR_REQUIRE(lens_host[b] > PAST && lens_host[b] <= max_len, "sequence %d has length %d (need %d < len <= max_len)", b, lens_host[b], PAST);
-    longest = std::max(longest, (int)lens_host[b]);
-  }
-  *n_win = (longest - PAST + CUR - 1) / CUR;
-  return GLAMR_OK;
-}
-}  // namespace
-
 extern "C" int glamr_nets_infill_taped(glamr_nets* h, int B, int max_len, const int32_t* lens_host, const float* body_pose, const float* visible,
                                        const float* motion_eps, int n_win_max, float* out_pose, void* tape_, void* stream_) {
   GLAMR_REQUIRE(h && lens_host && body_pose && visible && motion_eps && out_pose && tape_, "null argument");
   GLAMR_REQUIRE(B > 0 && max_len > PAST, "need n_seq > 0 and max_len > %d", PAST);
   int n_win = 0;
-  RC(tape_windows(lens_host, B, max_len, &n_win));
+  RC(count_windows(lens_host, B, max_len, &n_win));
   GLAMR_REQUIRE(n_win <= n_win_max, "motion_eps holds %d windows per sequence, %d needed", n_win_max, n_win);
   hipStream_t st = static_cast<hipStream_t>(stream_);
-  tl_fp32 = h->fp32_only ? 1 : 0;
-  tl_free = 0;
+  const Plan plan{st, h->fp32_only, false, true};      // every activation of every window is kept: the separate kernels at any number of rows
   Tape t = tape_layout(B, max_len, static_cast<char*>(tape_));
-  // (a caller capturing this stream -- the latent-optimisation mode replays its iteration as a HIP graph -- gets the lengths uploaded from
-  // the handle's pinned table, as glamr_nets_infer does: a copy node must not read pageable memory that is gone at replay)
-  const int32_t* lens_src = lens_host;
-  {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (st != nullptr && hipStreamIsCapturing(st, &cap) == hipSuccess && cap == hipStreamCaptureStatusActive) {
-      std::lock_guard<std::mutex> lock(h->graph_mu);
-      GLAMR_REQUIRE(h->capture_lens && h->capture_lens_used + (size_t)B <= CAPTURE_LENS_INTS,
-                    "the handle's table for calls recorded into caller graphs is full (%zu lengths); destroy and re-create the handle", CAPTURE_LENS_INTS);
-      int32_t* pinned = h->capture_lens + h->capture_lens_used;
-      h->capture_lens_used += (size_t)B;
-      std::memcpy(pinned, lens_host, (size_t)B * sizeof(int32_t));
-      lens_src = pinned;
-    }
-  }
-  GLAMR_HIP_CHECK(hipMemcpyAsync(t.lens, lens_src, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
+  bool capturing = false;
+  RC(stage_lens(h, st, lens_host, B, t.lens, false, &capturing));
   hipLaunchKernelGGL(pose_in_kernel, dim3(B, t.Tpad), dim3(64), 0, st, body_pose, max_len, t.Tpad, t.pose);
   for (int i = 0; i < n_win; ++i) {
-    WinTape& w = t.win[i];
+    const WinTape& w = t.win[i];
     const int s = i * CUR;
     hipLaunchKernelGGL(window_gather_kernel, dim3(B, WIN), dim3(64), 0, st, t.pose, visible, t.lens, t.Tpad, max_len, s, w.x, w.mask);
-    RC(taped_window(h, st, w, B, motion_eps + (size_t)i * NZ, n_win_max * NZ));
+    RC(infiller_window(h, plan, w, B, GLAMR_VAE_INFER, motion_eps + (size_t)i * NZ, n_win_max * NZ, nullptr, nullptr));
     hipLaunchKernelGGL(window_scatter_kernel, dim3(B, CUR), dim3(64), 0, st, w.y, 128, t.lens, t.Tpad, s, t.pose);
   }
   hipLaunchKernelGGL(pose_out_kernel, dim3(B, max_len), dim3(64), 0, st, t.pose, max_len, t.Tpad, t.lens, out_pose);
@@ -1349,15 +1374,13 @@ extern "C" int glamr_nets_infill_backward(glamr_nets* h, int B, int max_len, con
   GLAMR_REQUIRE(h && lens_host && motion_eps && g_out_pose && g_motion_eps && tape_, "null argument");
   GLAMR_REQUIRE(B > 0 && max_len > PAST, "need n_seq > 0 and max_len > %d", PAST);
   int n_win = 0;
-  RC(tape_windows(lens_host, B, max_len, &n_win));
+  RC(count_windows(lens_host, B, max_len, &n_win));
   GLAMR_REQUIRE(n_win <= n_win_max, "motion_eps holds %d windows per sequence, %d needed", n_win_max, n_win);
   hipStream_t st = static_cast<hipStream_t>(stream_);
-  tl_fp32 = h->fp32_only ? 1 : 0;
-  tl_free = 0;
   Tape t = tape_layout(B, max_len, static_cast<char*>(tape_));
   GLAMR_HIP_CHECK(hipMemsetAsync(t.pose + t.values, 0, t.values * sizeof(float), st));            // every gradient starts at zero
   GLAMR_HIP_CHECK(hipMemsetAsync(g_motion_eps, 0, (size_t)B * n_win_max * NZ * sizeof(float), st));
-  TapeCtx c{h, st, &t};
+  TapeCtx c{h, Plan{st, h->fp32_only, false, true}, &t};
   hipLaunchKernelGGL(pose_out_bwd_kernel, dim3(B, t.Tpad), dim3(XLD), 0, st, g_out_pose, max_len, t.Tpad, t.lens, GR(t, t.pose));
   for (int i = n_win - 1; i >= 0; --i) {
     const WinTape& w = t.win[i];

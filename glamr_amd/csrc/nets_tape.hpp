@@ -5,8 +5,8 @@
 // (motion_infiller_vae.py:618-632): every window's context encoder, prior, reparameterisation and decoder, and the autoregression --
 // a window's output frames are the next window's past frames (:604-607).
 //
-// Included by nets.hip INSIDE its anonymous namespace (not a stand-alone header).  The forward below is the small-batch launch sequence of infiller_window (separate
-// GEMM / attention / LayerNorm kernels, all fp32 MFMA) with every activation of every window kept in a tape arena; the backward walks
+// Included by nets.hip INSIDE its anonymous namespace (not a stand-alone header).  The forward is infiller_window itself under a plan that keeps
+// every activation (separate GEMM / attention / LayerNorm kernels) on the slots of a tape arena, one set per window; the backward walks
 // the windows in reverse and each layer in reverse.  Linear layers: dX = dY W with the TRANSPOSED weight through the same GEMM kernel
 // (transposes are made once per handle, the first time a tape is asked for); weights are constants (no weight gradients).
 
@@ -201,16 +201,7 @@ __global__ void pose_out_bwd_kernel(const float* g_out, int max_len, int Tpad, c
   gpose[((size_t)b * Tpad + t) * XLD + c] = (c < 69 && t < max_len && t < lens[b]) ? g_out[((size_t)b * max_len + t) * 69 + c] : 0.0f;
 }
 
-// ---- tape layout --------------------------------------------------------------------------------------------------------------------
-struct EncTape { float *qkv, *att, *tmp1, *mid, *ff, *tmp2, *out; };
-struct DecTape { float *qkv, *att_s, *tmp_s, *xa, *qbuf, *ctxkv, *att_c, *tmp_c, *xb, *ff, *tmp_f, *xc; };
-struct WinTape {
-  float *x, *h0; EncTape enc[2];
-  float *p_ctxkv, *p_att, *p_tmp1, *p_x1, *p_a, *p_ff, *p_tmp2, *p_b, *pz, *z;
-  float *zproj, *q0; DecTape dec[2];
-  float *o1, *o2, *y;
-  unsigned char* mask;
-};
+// ---- tape layout (WinTape: the slots of one window, nets.hip) --------------------------------------------------------------------
 struct Tape {
   float* pose; int* lens; int Tpad, n_win; size_t values, total;      // `values` floats of activations, then the same layout again for their gradients
   std::vector<WinTape> win;
@@ -220,15 +211,15 @@ inline float* GR(const Tape& t, float* v) { return v + t.values; }
 
 Tape tape_layout(int B, int max_len, char* base) {
   Tape t;
-  t.n_win = std::max(1, (max_len - PAST + CUR - 1) / CUR);
-  t.Tpad = std::max(max_len, (t.n_win - 1) * CUR + WIN);
+  t.n_win = std::max(1, windows_of(max_len));
+  t.Tpad = tpad_of(max_len);
   float* fb = reinterpret_cast<float*>(base);
   size_t off = 0;
   auto take = [&](size_t n) { float* p = fb + off; off += (n + 63) / 64 * 64; return p; };
   const size_t MW = (size_t)B * WIN, MC = (size_t)B * CUR, M2 = (size_t)B * 2;
   t.pose = take((size_t)B * t.Tpad * XLD);
   t.win.resize(t.n_win);
-  for (WinTape& w : t.win) {
+  for (WinTape& w : t.win) {      // (the posterior slots stay null: the tape runs GLAMR_VAE_INFER only)
     w.x = take(MW * XLD); w.h0 = take(MW * D);
     for (EncTape& e : w.enc) { e.qkv = take(MW * 3 * D); e.att = take(MW * D); e.tmp1 = take(MW * D); e.mid = take(MW * D); e.ff = take(MW * FF); e.tmp2 = take(MW * D); e.out = take(MW * D); }
     w.p_ctxkv = take(MW * 2 * D); w.p_att = take(M2 * D); w.p_tmp1 = take(M2 * D); w.p_x1 = take(M2 * D); w.p_a = take(M2 * D); w.p_ff = take(M2 * FF);
@@ -276,82 +267,26 @@ const Lin* transposed(glamr_nets* h, const Lin& L) {
   return &h->lin_T.emplace(&L, T).first->second;
 }
 
-struct TapeCtx { glamr_nets* h; hipStream_t st; const Tape* t; };
+struct TapeCtx { glamr_nets* h; Plan p; const Tape* t; };
 inline unsigned blocks(size_t n) { return (unsigned)((n + 255) / 256); }
 
 // dX += act'(.) dY W  (and dR += dY for a residual added after the activation).  dY is modified in place when the layer has a ReLU.
 int lin_bwd(const TapeCtx& c, const Lin& L, float* dY, int ldy, const float* Y, int act, float* dX, int ldx, int M, float* dR = nullptr) {
-  if (dR) hipLaunchKernelGGL(acc_kernel, dim3(blocks((size_t)M * ldy)), dim3(256), 0, c.st, dR, dY, (size_t)M * ldy);      // (ldy == ldr == the row width)
-  if (act == ACT_RELU) hipLaunchKernelGGL(relu_mask_kernel, dim3(blocks((size_t)M * ldy)), dim3(256), 0, c.st, dY, Y, (size_t)M * ldy);
+  if (dR) hipLaunchKernelGGL(acc_kernel, dim3(blocks((size_t)M * ldy)), dim3(256), 0, c.p.st, dR, dY, (size_t)M * ldy);      // (ldy == ldr == the row width)
+  if (act == ACT_RELU) hipLaunchKernelGGL(relu_mask_kernel, dim3(blocks((size_t)M * ldy)), dim3(256), 0, c.p.st, dY, Y, (size_t)M * ldy);
   if (!dX) return GLAMR_OK;
   const Lin* T = transposed(c.h, L);
   if (!T) return fail(GLAMR_E_HIP, "could not build the transposed weights of a layer");
   if (T->K > ldy) return fail(GLAMR_E_INVALID, "lin_bwd: gradient rows of %d floats, %d needed", ldy, T->K);
-  return lin(c.st, *T, dY, ldy, dX, ldx, M, ACT_NONE, dX, ldx, nullptr, 1, 0, -1, -1, true);      // accumulates through the residual input (the row-scaled one-wave split-fp16 kernel)
+  return lin(c.p, *T, dY, ldy, dX, ldx, M, ACT_NONE, {.R = dX, .ldr = ldx, .bwd = true});      // accumulates through the residual input (the row-scaled one-wave split-fp16 kernel)
 }
 int ln_bwd(const TapeCtx& c, const LN& n, const float* dY, const float* X, const float* R, float* dX, float* dR, int rows) {
-  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, c.st, dY, X, R, n.g, dX, dR, rows);
+  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, c.p.st, dY, X, R, n.g, dX, dR, rows);
   return GLAMR_OK;
 }
 void attn_bwd(const TapeCtx& c, const float* Q, int ldq, const float* K, const float* V, int ldk, const unsigned char* mask, const float* dO, float* dQ, float* dK,
               float* dV, int B, int Lq, int Lk, int q_shared) {
-  hipLaunchKernelGGL(attention_bwd_kernel, dim3(B, 8), dim3(256), 0, c.st, Q, ldq, K, V, ldk, mask, dO, D, dQ, dK, dV, Lq, Lk, q_shared);
-}
-
-// ---- forward of one window, every activation kept (mirrors infiller_window / encoder_layer / decoder_layer, small-batch path) -------
-int taped_window(glamr_nets* h, hipStream_t st, WinTape& w, int B, const float* eps, int eps_stride) {
-  const int M = B * WIN, MC = B * CUR;
-  RC(lin(st, h->enc_in, w.x, XLD, w.h0, D, M, ACT_NONE, nullptr, 0, h->enc_pe, -WIN, D));
-  const float* hin = w.h0;
-  for (int l = 0; l < 2; ++l) {
-    const EncLayer& E = h->enc[l];
-    EncTape& e = w.enc[l];
-    RC(lin(st, E.qkv, hin, D, e.qkv, 3 * D, M));
-    launch_attention(dim3(B, 8), dim3(64), 0, st, e.qkv, 3 * D, e.qkv + D, e.qkv + 2 * D, 3 * D, w.mask, e.att, D, WIN, WIN, 0);
-    RC(lin(st, E.o, e.att, D, e.tmp1, D, M));
-    RC(ln(st, e.tmp1, hin, E.n1, e.mid, M));
-    RC(lin(st, E.f1, e.mid, D, e.ff, FF, M, ACT_RELU));
-    RC(lin(st, E.f2, e.ff, FF, e.tmp2, D, M));
-    RC(ln(st, e.tmp2, e.mid, E.n2, e.out, M));
-    hin = e.out;
-  }
-  const float* ctx = hin;
-  // prior
-  RC(lin(st, h->prior_kv, ctx, D, w.p_ctxkv, 2 * D, M));
-  launch_attention(dim3(B, 8), dim3(64), 0, st, h->prior_q, D, w.p_ctxkv, w.p_ctxkv + D, 2 * D, w.mask, w.p_att, D, 2, WIN, 1);
-  RC(lin(st, h->prior_o, w.p_att, D, w.p_tmp1, D, B * 2));
-  hipLaunchKernelGGL(tile_rows_kernel, dim3((B * 2 * D + 255) / 256), dim3(64), 0, st, w.p_x1, h->prior_x1, 2, B * 2 * D);
-  RC(ln(st, w.p_tmp1, w.p_x1, h->prior_n2, w.p_a, B * 2));
-  RC(lin(st, h->prior_f1, w.p_a, D, w.p_ff, FF, B * 2, ACT_RELU));
-  RC(lin(st, h->prior_f2, w.p_ff, FF, w.p_tmp2, D, B * 2));
-  RC(ln(st, w.p_tmp2, w.p_a, h->prior_n3, w.p_b, B * 2));
-  RC(lin(st, h->prior_pz, w.p_b, D, w.pz, D, B * 2));
-  hipLaunchKernelGGL(reparam_infiller_kernel, dim3(B), dim3(64), 0, st, w.pz, eps, eps_stride, w.z, B);
-  // decoder
-  RC(lin(st, h->dec_z, w.z, NZ, w.zproj, D, B));
-  hipLaunchKernelGGL(build_queries_kernel, dim3(B, CUR), dim3(64), 0, st, w.zproj, h->dec_pe, w.q0);
-  const float* xin = w.q0;
-  for (int l = 0; l < 2; ++l) {
-    const DecLayer& Dl = h->dec[l];
-    DecTape& d = w.dec[l];
-    RC(lin(st, Dl.sa_qkv, xin, D, d.qkv, 3 * D, MC));
-    launch_attention(dim3(B, 8), dim3(64), 0, st, d.qkv, 3 * D, d.qkv + D, d.qkv + 2 * D, 3 * D, (const unsigned char*)nullptr, d.att_s, D, CUR, CUR, 0);
-    RC(lin(st, Dl.sa_o, d.att_s, D, d.tmp_s, D, MC));
-    RC(ln(st, d.tmp_s, xin, Dl.n1, d.xa, MC));
-    RC(lin(st, Dl.ca_q, d.xa, D, d.qbuf, D, MC));
-    RC(lin(st, Dl.ca_kv, ctx, D, d.ctxkv, 2 * D, M));
-    launch_attention(dim3(B, 8), dim3(64), 0, st, d.qbuf, D, d.ctxkv, d.ctxkv + D, 2 * D, w.mask, d.att_c, D, CUR, WIN, 0);
-    RC(lin(st, Dl.ca_o, d.att_c, D, d.tmp_c, D, MC));
-    RC(ln(st, d.tmp_c, d.xa, Dl.n2, d.xb, MC));
-    RC(lin(st, Dl.f1, d.xb, D, d.ff, FF, MC, ACT_RELU));
-    RC(lin(st, Dl.f2, d.ff, FF, d.tmp_f, D, MC));
-    RC(ln(st, d.tmp_f, d.xb, Dl.n3, d.xc, MC));
-    xin = d.xc;
-  }
-  RC(lin(st, h->out1, xin, D, w.o1, FF, MC, ACT_RELU));
-  RC(lin(st, h->out2, w.o1, FF, w.o2, D, MC, ACT_RELU));
-  RC(lin(st, h->outfc, w.o2, D, w.y, 128, MC));
-  return GLAMR_OK;
+  hipLaunchKernelGGL(attention_bwd_kernel, dim3(B, 8), dim3(256), 0, c.p.st, Q, ldq, K, V, ldk, mask, dO, D, dQ, dK, dV, Lq, Lk, q_shared);
 }
 
 // ---- backward of one window: GR(w.y) holds dL/dy on entry; on return GR(w.x) holds dL/dx and deps has received dL/d eps -----------------
@@ -383,9 +318,9 @@ int taped_window_bwd(const TapeCtx& c, const WinTape& w, int B, const float* eps
     attn_bwd(c, d.qkv, 3 * D, d.qkv + D, d.qkv + 2 * D, 3 * D, nullptr, G(d.att_s), G(d.qkv), G(d.qkv) + D, G(d.qkv) + 2 * D, B, CUR, CUR, 0);
     RC(lin_bwd(c, Dl.sa_qkv, G(d.qkv), 3 * D, nullptr, ACT_NONE, G(xin), D, MC));
   }
-  hipLaunchKernelGGL(build_queries_bwd_kernel, dim3(B), dim3(D), 0, c.st, G(w.q0), G(w.zproj));
+  hipLaunchKernelGGL(build_queries_bwd_kernel, dim3(B), dim3(D), 0, c.p.st, G(w.q0), G(w.zproj));
   RC(lin_bwd(c, h->dec_z, G(w.zproj), D, nullptr, ACT_NONE, G(w.z), NZ, B));
-  hipLaunchKernelGGL(reparam_infiller_bwd_kernel, dim3(B), dim3(NZ), 0, c.st, w.pz, eps, eps_stride, G(w.z), G(w.pz), deps, deps_stride);
+  hipLaunchKernelGGL(reparam_infiller_bwd_kernel, dim3(B), dim3(NZ), 0, c.p.st, w.pz, eps, eps_stride, G(w.z), G(w.pz), deps, deps_stride);
   // prior
   RC(lin_bwd(c, h->prior_pz, G(w.pz), D, nullptr, ACT_NONE, G(w.p_b), D, B * 2));
   RC(ln_bwd(c, h->prior_n3, G(w.p_b), w.p_tmp2, w.p_a, G(w.p_tmp2), G(w.p_a), B * 2));

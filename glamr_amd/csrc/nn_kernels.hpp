@@ -1059,17 +1059,14 @@ __global__ __launch_bounds__(512) void lstm_mfma_kernel(LstmArgs a, int n_seq) {
 // off): a sequence alone and the same sequence inside a small batch then agree to the bit.  Small M is launch / latency bound either way.
 constexpr int SMALL_ROWS = 2048;
 
-inline int launch_gemm(hipStream_t st, const float* X, int ldx, const float* W, const float* bias, float* Y, int ldy, int M, int N, int K,
-                       int act = ACT_NONE, const float* R = nullptr, int ldr = 0, const float* rowbias = nullptr, int rows_per_group = 1, int ldrb = 0,
-                       const unsigned short* Ws = nullptr) {
+// a.Ws / a.ws_plane: the weight's fp16 planes when it has them (ws_plane = ceil64(N) K elements)
+inline int launch_gemm(hipStream_t st, GemmArgs a) {
+  const int M = a.M, N = a.N, K = a.K;
   if (M <= 0) return GLAMR_OK;
-  if (K % GT_K != 0 || ldx % 4 != 0) return fail(GLAMR_E_INVALID, "gemm: K=%d must be a multiple of %d and ldx=%d of 4", K, GT_K, ldx);
-  GemmArgs a{X, W, bias, rowbias, R, Y, M, N, K, ldx, ldy, ldr, rows_per_group, ldrb, act};
+  if (K % GT_K != 0 || a.ldx % 4 != 0) return fail(GLAMR_E_INVALID, "gemm: K=%d must be a multiple of %d and ldx=%d of 4", K, GT_K, a.ldx);
   const int npad = (N + GT_N - 1) / GT_N * GT_N;
-  if (Ws && M >= SMALL_ROWS) {
+  if (a.Ws && M >= SMALL_ROWS) {
     // tall activations: the split-bf16 kernel
-    a.Ws = Ws;
-    a.ws_plane = (size_t)npad * K;
     if (npad % 128 == 0 && (size_t)(M / 128) * (npad / 128) >= 512)
       hipLaunchKernelGGL((gemm_split_kernel<2>), dim3(npad / 128, ((M + 127) / 128 + 7) / 8 * 8), dim3(256), 0, st, a);
     else
@@ -1078,6 +1075,8 @@ inline int launch_gemm(hipStream_t st, const float* X, int ldx, const float* W, 
   }
   // (measured and dropped, round 4: the K loop of a tile over two groups of four waves for grids of a handful of workgroups -- 13.3 against 12.4 us
   // per call at M = 50: these calls are launch + latency, not the chain of fp32 MFMAs)
+  a.Ws = nullptr;      // (the fp32 kernel has no use for the planes)
+  a.ws_plane = 0;
   hipLaunchKernelGGL(gemm_small_kernel, dim3((N + 31) / 32, (M + 31) / 32), dim3(256), 0, st, a);
   return GLAMR_OK;
 }

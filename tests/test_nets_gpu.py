@@ -360,6 +360,25 @@ def test_infiller_gradient_wrt_the_latent_matches_reference_autograd(priors, gol
     assert np.abs(both[1, :alone.shape[0]] - alone).max() < 1e-5
 
 
+@pytest.mark.parametrize('lens', [[120], [300, 47, 120]])
+def test_taped_pose_is_the_plain_pose_bit_for_bit_in_small_batches(priors, lens):
+    """Below SMALL_ROWS / 50 sequences the plain infiller runs the separate kernels the tape always runs, through the same window forward
+    (infiller_window of nets.hip, once on workspace aliases and once on the tape's slots): the two poses are the same bits."""
+    dev = torch.device('cuda:0')
+    T = max(lens)
+    ins = [mg.net_inputs(n, seed=i) for i, n in enumerate(lens)]
+    pose = torch.zeros(len(lens), T, 69, device=dev)
+    vis = torch.zeros(len(lens), T, device=dev)
+    meps = torch.zeros(len(lens), max(x['in_motion_latent'].shape[0] for x in ins), 128, device=dev)
+    for i, x in enumerate(ins):
+        pose[i, :lens[i]] = torch.tensor(x['in_body_pose'][0])
+        vis[i, :lens[i]] = torch.tensor(x['frame_mask'][0]).float()
+        meps[i, :x['in_motion_latent'].shape[0]] = torch.tensor(x['in_motion_latent'])
+    taped, _ = priors.infill_taped(pose, vis, lens, meps)
+    plain = priors.infer(pose, vis, lens, motion_eps=meps, traj_eps=None, traj=False)['pose']
+    assert torch.equal(taped, plain)
+
+
 def test_range_analysis_selects_the_fp32_kernels_for_a_checkpoint_outside_fp16(asset_root, priors, golden, monkeypatch):
     """The fp16-split kernels hold every fp32 operand as two fp16 numbers: fine for O(1) activations and O(0.05) weights, wrong above 65 504.
     glamr_nets_create bounds, from the weights alone, every value those kernels could convert; a checkpoint that can leave fp16's range runs
