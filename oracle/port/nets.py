@@ -76,7 +76,7 @@ class BiLSTM(nn.Module):
         self.rnn_b = nn.LSTMCell(in_dim, out_dim // 2)
 
     def _run(self, cell, x, reverse):
-        h = torch.zeros((x.size(1), cell.hidden_size), device=x.device)
+        h = torch.zeros((x.size(1), cell.hidden_size), device=x.device, dtype=x.dtype)
         c = torch.zeros_like(h)
         out = [None] * x.size(0)
         order = range(x.size(0) - 1, -1, -1) if reverse else range(x.size(0))
@@ -354,7 +354,7 @@ class TrajDataDecoder(nn.Module):
             hv0 = data['local_traj_tp'][:1, :, -2:].unsqueeze(2).repeat((1, 1, sample_num, 1))
         else:
             xy0 = torch.zeros_like(out[:1, ..., :2])
-            hv0 = torch.tensor([0., 1.], device=out.device).expand_as(out[:1, ..., -2:])
+            hv0 = torch.tensor([0., 1.], device=out.device, dtype=out.dtype).expand_as(out[:1, ..., -2:])
         out[..., :2] = torch.cat([xy0, x[1:, ..., :2]], dim=0)
         out[..., -2:] = torch.cat([hv0, x[1:, ..., -2:]], dim=0)
         if mode != 'infer':
