@@ -1,5 +1,9 @@
-"""MI355X parity tests of the SMPL kernels (glamr_smpl_* through the ctypes ABI) against the CPU oracle and the
-reference-generated fixtures.  Tolerance: joints and vertices within 1e-4 m (BASELINE.json north_star); achieved ~1e-6."""
+"""MI355X parity tests of the SMPL kernels (glamr_smpl_* through the ctypes ABI) against the fp32 CPU restatement and the reference-generated
+fixtures.  Against the restatement on the same inputs the bound is the measured one of tests/smpl_ref_common.py (16 x the restatement's own
+rounding against fp64, 1.2e-5 to 1.8e-5 m at ~1 m) plus one such rounding for the fp32 reference itself; against the fixture files, whose
+reference is the fp32 reference run, and for the rigid-root identity (two device results and a torch rotation) it stays 1e-4 m (BASELINE.json
+north_star).  The comparison against fp64, the call variants, the pose families and the per-(frame, joint) gradient measures are in
+tests/test_smpl_fp64_gpu.py."""
 import os
 import numpy as np
 import pytest
@@ -7,9 +11,15 @@ import torch
 
 from oracle import make_golden as mg
 from oracle.port import build
+from tests import smpl_ref_common as sc
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
+
+
+def _tol(name, model='fixture'):
+    """Anchored call at ~1 m against the fp32 restatement: the device's 16 floors against fp64 plus the restatement's own one."""
+    return (sc.FLOOR_FACTOR + 1) * sc.FWD_FLOOR[model]['1m_noscale'][name]
 
 
 @pytest.fixture(scope='module')
@@ -54,15 +64,15 @@ def test_smpl_matches_oracle_full_mesh(models, B):
     ref = ora(global_orient=pose[:, :3], body_pose=pose[:, 3:], betas=betas, root_trans=trans, return_full_pose=True)
     out = mine(global_orient=pose[:, :3].to(dev), body_pose=pose[:, 3:].to(dev), betas=betas.to(dev), root_trans=trans.to(dev))
     assert out.vertices.shape == (B, 6890, 3) and out.joints.shape == (B, 26, 3)
-    assert _err(out.joints, ref.joints) < TOL
-    assert _err(out.vertices, ref.vertices) < TOL
+    assert _err(out.joints, ref.joints) < _tol('joints')
+    assert _err(out.vertices, ref.vertices) < _tol('verts')
     # joints-only call: skins only the vertices the mapped joints depend on (a different summation grouping of the regressed
     # joints, hence last-bit differences from the full-mesh call)
     j_only = mine(global_orient=pose[:, :3].to(dev), body_pose=pose[:, 3:].to(dev), betas=betas.to(dev), root_trans=trans.to(dev),
                   return_verts=False)
     assert j_only.vertices is None
     assert _err(j_only.joints, out.joints) < 2e-6
-    assert _err(j_only.joints, ref.joints) < TOL
+    assert _err(j_only.joints, ref.joints) < _tol('joints')
 
 
 def test_smpl_rigid_root_identity_full_size(models):
@@ -218,7 +228,9 @@ def test_sparse_regressors_as_the_real_model_stores_them(tmp_path):
     jonly = mine(global_orient=pose[:, :3].to(dev), body_pose=pose[:, 3:].to(dev), betas=betas.to(dev), root_trans=trans.to(dev), return_verts=False)
     e = (_err(full.joints, ref.joints), _err(full.vertices, ref.vertices), _err(jonly.joints, ref.joints))
     print('sparse regressors: joints %.2e, vertices %.2e, joints-only tiling %.2e' % e)
-    assert max(e) < TOL
+    # (the fixture model with cut regressors: between the two models of the common module, held to the looser of their bounds)
+    tj, tv = (max(_tol(n, 'fixture'), _tol(n, 'conditioned')) for n in ('joints', 'verts'))
+    assert e[0] < tj and e[1] < tv and e[2] < tj
     # gradients w.r.t. body pose / betas through the joints-only tiling
     wj = torch.randn(B, 26, 3, generator=gen)
     bp_c, be_c = pose[:, 3:].clone().requires_grad_(True), betas.clone().requires_grad_(True)
