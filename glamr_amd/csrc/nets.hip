@@ -1054,67 +1054,94 @@ int infiller_window(glamr_nets* h, const Plan& p, const WinTape& w, int B, int m
 
 #include "nets_tape.hpp"
 
-void bilstm(const Plan& p, const float* G, float* const hh[2], const int* lens, float* H, int max_len, int B) {
-  LstmArgs la{G, hh[0], hh[1], lens, H, max_len};
+// tape: when given, the TAPE instances of the same kernels (the same arithmetic plus the stores of every step's gates and cell state)
+void bilstm(const Plan& p, const float* G, float* const hh[2], const int* lens, float* H, int max_len, int B, float* tape = nullptr) {
+  LstmArgs la{G, hh[0], hh[1], lens, H, max_len, tape};
   // large batches: 16 sequences per workgroup on the matrix cores; small ones: one sequence per workgroup keeps every CU busy
-  if (B >= 512 && !p.fp32) hipLaunchKernelGGL(lstm_mfma_kernel, dim3((B + 15) / 16, 2), dim3(512), 0, p.st, la, B);
-  else hipLaunchKernelGGL(lstm_kernel, dim3(B, 2), dim3(512), 0, p.st, la);
+  if (B >= 512 && !p.fp32) {
+    if (tape) hipLaunchKernelGGL(lstm_mfma_kernel<true>, dim3((B + 15) / 16, 2), dim3(512), 0, p.st, la, B);
+    else hipLaunchKernelGGL(lstm_mfma_kernel<false>, dim3((B + 15) / 16, 2), dim3(512), 0, p.st, la, B);
+  } else {
+    if (tape) hipLaunchKernelGGL(lstm_kernel<true>, dim3(B, 2), dim3(512), 0, p.st, la);
+    else hipLaunchKernelGGL(lstm_kernel<false>, dim3(B, 2), dim3(512), 0, p.st, la);
+  }
 }
 
-// ---- the trajectory predictor on joint rows w.tx [B][max_len][96] -------------------------------------------------------------------
+// The activation slots of the trajectory predictor's inference pass (traj_pass below writes them, traj_backward of traj_tape.hpp reads them):
+// aliases of a few workspace buffers otherwise (traj_slots), distinct buffers in a tape.  lstm[l]: the recurrence tape of layer l (null: untaped).
+struct TrajSlots {
+  float *x, *h0, *h1, *h2, *ctx;      // joint rows [MT][96]; in_mlp output, the two bi-LSTM outputs, the context [MT][256]
+  float *g, *tmp;                     // scratch: gate pre-activations / hidden rows [MT][1024], [MT][256]
+  float *dec;                         // decoder MLP output [MT][256]
+  float *mean, *pr1, *pr2, *pz, *z, *zrow;      // per sequence: context mean [256], prior_mlp hidden [512] and output [256], p(z) [256], z [128], W_z z + b [512]
+  float *raw, *scr;                   // out_fc rows [MT][64], scan scratch [MT][3]
+  float* lstm[2];
+};
+TrajSlots traj_slots(const Ws& w) {
+  return TrajSlots{w.tx, w.th, w.th, w.th, w.th, w.tg, w.tq, w.tq, w.tmean, w.trow, w.tmean, w.pz, w.z, w.trow, w.traw, w.tscr, {nullptr, nullptr}};
+}
+
+// ---- the trajectory predictor on joint rows s.x [B][max_len][96] --------------------------------------------------------------------
 // lens_run: frames the recurrent layers and the temporal means cover.  mode as above; modes 1 / 2 need w.e6 (encoder rows) and use
-// `init` (first row of the ground-truth local trajectory) for the first output row.
-int traj_pass(glamr_nets* h, const Plan& p, Ws& w, int B, int max_len, const int* lens_run, int mode, const float* eps, float* q_out, float* p_out,
+// `init` (first row of the ground-truth local trajectory) for the first output row.  This is the ONLY launch sequence of the predictor: the
+// workspace path and the taped path (distinct slots, the TAPE instances of the recurrence) both run it, on the same kernels.
+int traj_pass(glamr_nets* h, const Plan& p, Ws& w, const TrajSlots& s, int B, int max_len, const int* lens_run, int mode, const float* eps, float* q_out, float* p_out,
               const float* init, int ldinit, float* out_orig, float* out_local, float* out_trans, float* out_orient, float* out_orient_q) {
   const int MT = B * max_len;
   hipStream_t st = p.st;
-  RC(mlp2(p, h->t_in1, h->t_in2, nullptr, w.tx, XLD, nullptr, w.th, w.tg, w.tq, MT, ACT_RELU));
-  for (int l = 0; l < 2; ++l) {
-    RC(lin(p, h->t_ih[l], w.th, D, w.tg, 1024, MT));
-    bilstm(p, w.tg, h->t_hh[l], lens_run, w.th, max_len, B);
+  RC(mlp2(p, h->t_in1, h->t_in2, nullptr, s.x, XLD, nullptr, s.h0, s.g, s.tmp, MT, ACT_RELU));
+  {
+    const float* in[2] = {s.h0, s.h1};
+    float* out[2] = {s.h1, s.h2};
+    for (int l = 0; l < 2; ++l) {
+      RC(lin(p, h->t_ih[l], in[l], D, s.g, 1024, MT));
+      bilstm(p, s.g, h->t_hh[l], lens_run, out[l], max_len, B, s.lstm[l]);
+    }
   }
-  RC(mlp2(p, h->t_out1, h->t_out2, nullptr, w.th, D, nullptr, w.th, w.tg, w.tq, MT, ACT_RELU));       // context [B][max_len][256]
+  RC(mlp2(p, h->t_out1, h->t_out2, nullptr, s.h2, D, nullptr, s.ctx, s.g, s.tmp, MT, ACT_RELU));       // context [B][max_len][256]
   if (mode != GLAMR_VAE_INFER) {
     // posterior (DataEncoder.forward :160-199): [t_h, aa(q_h)] -> in_mlp -> 2 bi-LSTM -> out_mlp; fused with the context, mean over time
-    RC(lin(p, h->te_in1, w.e6, 32, w.tg, FF, MT, ACT_RELU));
-    RC(lin(p, h->te_in2, w.tg, FF, w.te, D, MT, ACT_RELU));
+    RC(lin(p, h->te_in1, w.e6, 32, s.g, FF, MT, ACT_RELU));
+    RC(lin(p, h->te_in2, s.g, FF, w.te, D, MT, ACT_RELU));
     for (int l = 0; l < 2; ++l) {
-      RC(lin(p, h->te_ih[l], w.te, D, w.tg, 1024, MT));
-      bilstm(p, w.tg, h->te_hh[l], lens_run, w.te, max_len, B);
+      RC(lin(p, h->te_ih[l], w.te, D, s.g, 1024, MT));
+      bilstm(p, s.g, h->te_hh[l], lens_run, w.te, max_len, B);
     }
-    RC(lin(p, h->te_out1, w.te, D, w.tg, FF, MT, ACT_RELU));
-    RC(lin(p, h->te_out2, w.tg, FF, w.tcat, FF, MT, ACT_RELU));     // columns [0,256) of the fused rows
-    hipLaunchKernelGGL(copy_cols_kernel, dim3(((size_t)MT * D + 255) / 256), dim3(256), 0, st, w.th, D, w.tcat, FF, D, (size_t)MT * D);
-    RC(lin(p, h->te_f1, w.tcat, FF, w.tg, FF, MT, ACT_RELU));
-    RC(lin(p, h->te_f2, w.tg, FF, w.te, D, MT, ACT_RELU));
+    RC(lin(p, h->te_out1, w.te, D, s.g, FF, MT, ACT_RELU));
+    RC(lin(p, h->te_out2, s.g, FF, w.tcat, FF, MT, ACT_RELU));     // columns [0,256) of the fused rows
+    hipLaunchKernelGGL(copy_cols_kernel, dim3(((size_t)MT * D + 255) / 256), dim3(256), 0, st, s.ctx, D, w.tcat, FF, D, (size_t)MT * D);
+    RC(lin(p, h->te_f1, w.tcat, FF, s.g, FF, MT, ACT_RELU));
+    RC(lin(p, h->te_f2, s.g, FF, w.te, D, MT, ACT_RELU));
     hipLaunchKernelGGL(masked_mean_kernel, dim3(B, 4), dim3(64), 0, st, w.te, max_len, lens_run, w.tmean);
     RC(lin(p, h->te_qz, w.tmean, D, w.tqz, D, B));
     if (q_out) GLAMR_HIP_CHECK(hipMemcpyAsync(q_out, w.tqz, (size_t)B * D * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
-  hipLaunchKernelGGL(masked_mean_kernel, dim3(B, 4), dim3(64), 0, st, w.th, max_len, lens_run, w.tmean);
-  RC(lin(p, h->t_pr1, w.tmean, D, w.trow, FF, B, ACT_RELU));
-  RC(lin(p, h->t_pr2, w.trow, FF, w.tmean, D, B, ACT_RELU));
-  RC(lin(p, h->t_pz, w.tmean, D, w.pz, D, B));
-  if (p_out) GLAMR_HIP_CHECK(hipMemcpyAsync(p_out, w.pz, (size_t)B * D * sizeof(float), hipMemcpyDeviceToDevice, st));
-  if (mode == GLAMR_VAE_INFER) hipLaunchKernelGGL(reparam_traj_kernel, dim3(B), dim3(64), 0, st, w.pz, eps, w.z);
-  else if (mode == GLAMR_VAE_TRAIN) hipLaunchKernelGGL(reparam_traj_kernel, dim3(B), dim3(64), 0, st, w.tqz, eps, w.z);
-  else hipLaunchKernelGGL(mode_traj_kernel, dim3(B), dim3(NZ), 0, st, w.tqz, w.z);
-  RC(lin(p, h->t_dz, w.z, NZ, w.trow, FF, B));      // W_z z + b, one row per sequence
+  hipLaunchKernelGGL(masked_mean_kernel, dim3(B, 4), dim3(64), 0, st, s.ctx, max_len, lens_run, s.mean);
+  RC(lin(p, h->t_pr1, s.mean, D, s.pr1, FF, B, ACT_RELU));
+  RC(lin(p, h->t_pr2, s.pr1, FF, s.pr2, D, B, ACT_RELU));
+  RC(lin(p, h->t_pz, s.pr2, D, s.pz, D, B));
+  if (p_out) GLAMR_HIP_CHECK(hipMemcpyAsync(p_out, s.pz, (size_t)B * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if (mode == GLAMR_VAE_INFER) hipLaunchKernelGGL(reparam_traj_kernel, dim3(B), dim3(64), 0, st, s.pz, eps, s.z);
+  else if (mode == GLAMR_VAE_TRAIN) hipLaunchKernelGGL(reparam_traj_kernel, dim3(B), dim3(64), 0, st, w.tqz, eps, s.z);
+  else hipLaunchKernelGGL(mode_traj_kernel, dim3(B), dim3(NZ), 0, st, w.tqz, s.z);
+  RC(lin(p, h->t_dz, s.z, NZ, s.zrow, FF, B));      // W_z z + b, one row per sequence
   // decoder MLP: relu(W_ctx ctx + [W_z z + b] of the sequence) -> relu(W_2 .): as ONE row-block launch (the 512-wide hidden rows stay in LDS:
   // 629 MB less written and read again per 1024 x 300 frames)
   if (!p.fp32 && MT >= SMALL_ROWS && max_len >= 64 && h->t_dctx.Ws && h->t_d2.Ws && h->t_dctx.K == D && h->t_dctx.N == FF && h->t_d2.K == FF && h->t_d2.N == D) {
-    RC(launch_rows(st, w.th, D, MT, D, h->t_dctx.Ws, (size_t)FF * D, h->t_dctx.b, w.trow, max_len, FF, h->t_d2.Ws, (size_t)D * FF, FF, h->t_d2.b, ACT_RELU,
-                   nullptr, D, nullptr, nullptr, w.tq, D));
+    RC(launch_rows(st, s.ctx, D, MT, D, h->t_dctx.Ws, (size_t)FF * D, h->t_dctx.b, s.zrow, max_len, FF, h->t_d2.Ws, (size_t)D * FF, FF, h->t_d2.b, ACT_RELU,
+                   nullptr, D, nullptr, nullptr, s.dec, D));
   } else {
-    RC(lin(p, h->t_dctx, w.th, D, w.tg, FF, MT, ACT_RELU, {.rowbias = w.trow, .rpg = max_len, .ldrb = FF}));
-    RC(lin(p, h->t_d2, w.tg, FF, w.tq, D, MT, ACT_RELU));
+    RC(lin(p, h->t_dctx, s.ctx, D, s.g, FF, MT, ACT_RELU, {.rowbias = s.zrow, .rpg = max_len, .ldrb = FF}));
+    RC(lin(p, h->t_d2, s.g, FF, s.dec, D, MT, ACT_RELU));
   }
-  RC(lin(p, h->t_dfc, w.tq, D, w.traw, 64, MT));
-  if (out_orig) hipLaunchKernelGGL(rows_out_kernel, dim3(MT), dim3(64), 0, st, w.traw, 64, MT, 11, out_orig);
-  hipLaunchKernelGGL(traj_to_global2_kernel, dim3(B), dim3(256), 0, st, w.traw, 64, max_len, lens_run, init, ldinit, 1, out_local, out_trans, out_orient,
-                     out_orient_q, w.tscr);
+  RC(lin(p, h->t_dfc, s.dec, D, s.raw, 64, MT));
+  if (out_orig) hipLaunchKernelGGL(rows_out_kernel, dim3(MT), dim3(64), 0, st, s.raw, 64, MT, 11, out_orig);
+  hipLaunchKernelGGL(traj_to_global2_kernel, dim3(B), dim3(256), 0, st, s.raw, 64, max_len, lens_run, init, ldinit, 1, out_local, out_trans, out_orient,
+                     out_orient_q, s.scr);
   return GLAMR_OK;
 }
+
+#include "traj_tape.hpp"
 
 }  // namespace
 
@@ -1179,7 +1206,7 @@ int enqueue_infer(glamr_nets* h, const Plan& p, Ws& w, int B, int max_len, int n
   Plan tp = p;
   tp.free = false;
   hipLaunchKernelGGL(fk_joints_kernel, dim3(B, (max_len + FK_FRAMES - 1) / FK_FRAMES), dim3(256), 0, st, w.pose, w.Tpad, max_len, w.lens, h->rest_joints, h->parents, w.tx);
-  return traj_pass(h, tp, w, B, max_len, w.lens, GLAMR_VAE_INFER, traj_eps, nullptr, nullptr, nullptr, 0, nullptr, out_local_traj, out_trans, out_orient, nullptr);
+  return traj_pass(h, tp, w, traj_slots(w), B, max_len, w.lens, GLAMR_VAE_INFER, traj_eps, nullptr, nullptr, nullptr, 0, nullptr, out_local_traj, out_trans, out_orient, nullptr);
 }
 }  // namespace
 
@@ -1308,7 +1335,7 @@ extern "C" int glamr_nets_traj_clip(glamr_nets* h, int B, int T, int mode, const
   }
   int ldinit = T * 11;
   if (io->init_row) { init = io->init_row; ldinit = 11; }      // :319-321 takes precedence
-  RC(traj_pass(h, plan, w, B, T, w.lens, mode, io->eps, io->q_z, io->p_z, init, ldinit, io->out_orig_local_traj, io->out_local_traj, io->out_trans,
+  RC(traj_pass(h, plan, w, traj_slots(w), B, T, w.lens, mode, io->eps, io->q_z, io->p_z, init, ldinit, io->out_orig_local_traj, io->out_local_traj, io->out_trans,
                io->out_orient, io->out_orient_q));
   if (io->z) GLAMR_HIP_CHECK(hipMemcpyAsync(io->z, w.z, (size_t)B * NZ * sizeof(float), hipMemcpyDeviceToDevice, st));
   GLAMR_HIP_CHECK(hipStreamSynchronize(st));          // `run` / `valid` are pageable host buffers
@@ -1389,6 +1416,59 @@ extern "C" int glamr_nets_infill_backward(glamr_nets* h, int B, int max_len, con
     RC(taped_window_bwd(c, w, B, motion_eps + (size_t)i * NZ, n_win_max * NZ, g_motion_eps + (size_t)i * NZ, n_win_max * NZ));
     hipLaunchKernelGGL(window_gather_bwd_kernel, dim3(B, WIN), dim3(XLD), 0, st, GR(t, w.x), t.lens, t.Tpad, s, GR(t, t.pose));
   }
+  GLAMR_HIP_CHECK(hipGetLastError());
+  return GLAMR_OK;
+}
+
+// ---- taped trajectory predictor: the inference pass with its activations and recurrence states kept + its vector-Jacobian product -----------
+namespace {
+int check_traj_lens(const int32_t* lens_host, int B, int max_len) {
+  for (int b = 0; b < B; ++b) GLAMR_REQUIRE(lens_host[b] >= 1 && lens_host[b] <= max_len, "sequence %d has length %d (need 1 <= len <= max_len)", b, lens_host[b]);
+  return GLAMR_OK;
+}
+}  // namespace
+
+extern "C" size_t glamr_nets_traj_tape_bytes(const glamr_nets* h, int n_seq, int max_len) {
+  if (!h || n_seq <= 0 || max_len <= 0) return 0;
+  return traj_tape_layout(n_seq, max_len, nullptr).total;
+}
+
+extern "C" int glamr_nets_traj_taped(glamr_nets* h, int B, int max_len, const int32_t* lens_host, const float* in_joint_pos, const float* in_body_pose,
+                                     const float* traj_eps, float* out_local_traj, void* tape_, void* stream_) {
+  GLAMR_REQUIRE(h && lens_host && traj_eps && out_local_traj && tape_, "null argument");
+  GLAMR_REQUIRE((in_joint_pos != nullptr) != (in_body_pose != nullptr), "exactly one of in_joint_pos and in_body_pose must be given");
+  GLAMR_REQUIRE(B > 0 && max_len > 0, "need n_seq > 0 and max_len > 0");
+  RC(check_traj_lens(lens_host, B, max_len));
+  RC(traj_transposes(h));
+  hipStream_t st = static_cast<hipStream_t>(stream_);
+  const Plan plan{st, h->fp32_only, false, false};      // the plan of glamr_nets_traj_clip and of the predictor inside glamr_nets_infer: the same kernels
+  TrajTape t = traj_tape_layout(B, max_len, static_cast<char*>(tape_));
+  bool capturing = false;
+  RC(stage_lens(h, st, lens_host, B, t.lens, false, &capturing));
+  const size_t MT = (size_t)B * max_len;
+  // (the recurrence kernels write a sequence's own frames only: rows past its end read as zeros by the backward)
+  GLAMR_HIP_CHECK(hipMemsetAsync(t.s.h1, 0, MT * D * sizeof(float), st));
+  GLAMR_HIP_CHECK(hipMemsetAsync(t.s.h2, 0, MT * D * sizeof(float), st));
+  if (in_joint_pos) {
+    hipLaunchKernelGGL(joints_in_kernel, dim3(B, max_len), dim3(XLD), 0, st, in_joint_pos, max_len, t.lens, t.s.x);
+  } else {
+    hipLaunchKernelGGL(pose_in_kernel, dim3(B, max_len), dim3(64), 0, st, in_body_pose, max_len, max_len, t.pose);
+    hipLaunchKernelGGL(fk_joints_kernel, dim3(B, (max_len + FK_FRAMES - 1) / FK_FRAMES), dim3(256), 0, st, t.pose, max_len, max_len, t.lens, h->rest_joints, h->parents, t.s.x);
+  }
+  Ws none{};                                              // (the posterior's buffers: inference mode does not touch them)
+  RC(traj_pass(h, plan, none, t.s, B, max_len, t.lens, GLAMR_VAE_INFER, traj_eps, nullptr, nullptr, nullptr, 0, nullptr, out_local_traj, nullptr, nullptr, nullptr));
+  GLAMR_HIP_CHECK(hipGetLastError());
+  return GLAMR_OK;
+}
+
+extern "C" int glamr_nets_traj_backward(glamr_nets* h, int B, int max_len, const int32_t* lens_host, const float* traj_eps, const float* g_local_traj,
+                                        float* g_eps, float* g_joint_pos, void* tape_, void* stream_) {
+  GLAMR_REQUIRE(h && lens_host && traj_eps && g_local_traj && g_eps && tape_, "null argument");
+  GLAMR_REQUIRE(B > 0 && max_len > 0, "need n_seq > 0 and max_len > 0");
+  RC(check_traj_lens(lens_host, B, max_len));
+  hipStream_t st = static_cast<hipStream_t>(stream_);
+  const TrajTape t = traj_tape_layout(B, max_len, static_cast<char*>(tape_));
+  RC(traj_backward_pass(h, Plan{st, h->fp32_only, false, true}, t, B, max_len, traj_eps, g_local_traj, g_eps, g_joint_pos));
   GLAMR_HIP_CHECK(hipGetLastError());
   return GLAMR_OK;
 }

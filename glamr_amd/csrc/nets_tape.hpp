@@ -1,7 +1,7 @@
 // Taped forward and explicit backward of the motion infiller: gradients of the generated body pose w.r.t. the latent draws
 // (`in_motion_latent`), for the latent-optimisation mode of the global optimiser (global_recon_model.py:43-44,155-158,434-437: the
-// infiller runs inside the Adam loop and `motion_latent` is a parameter; the trajectory predictor's output is detached by
-// get_pred_trajectory_base :396, so it needs no backward).  What torch autograd does through MotionInfillerVAE.inference_multi_step
+// infiller runs inside the Adam loop and `motion_latent` is a parameter; the reference detaches the trajectory predictor's output in
+// get_pred_trajectory_base :396 and never differentiates it -- traj_tape.hpp is the attached alternative).  What torch autograd does through MotionInfillerVAE.inference_multi_step
 // (motion_infiller_vae.py:618-632): every window's context encoder, prior, reparameterisation and decoder, and the autoregression --
 // a window's output frames are the next window's past frames (:604-607).
 //

@@ -904,8 +904,13 @@ struct LstmArgs {
   const int* lens;       // [n_seq]
   float* H;              // [n_seq][max_len][256]: cols [0,128) forward h_t, [128,256) backward h_t
   int max_len;
+  float* tape = nullptr; // TAPE instances only: [n_seq][max_len][2 directions][LSTM_TAPE = i f g o (post-activation) c][128], what the BPTT kernels of traj_tape.hpp read
 };
+constexpr int LSTM_TAPE = 5;
+__device__ __forceinline__ size_t lstm_tape_off(int seq, int max_len, int t, int dir) { return (((size_t)seq * max_len + t) * 2 + dir) * (LSTM_TAPE * 128); }
 
+// TAPE: the same instructions plus the stores of the step's gates and cell state (the taped forward of the trajectory predictor)
+template <bool TAPE = false>
 __global__ __launch_bounds__(512) void lstm_kernel(LstmArgs a) {
   __shared__ __attribute__((aligned(16))) float sh[128];
   __shared__ float sg[512];
@@ -946,6 +951,10 @@ __global__ __launch_bounds__(512) void lstm_kernel(LstmArgs a) {
       const float hnew = og * tanhf(c);
       sh[r] = hnew;
       Hb[(size_t)t * 256 + r] = hnew;
+      if constexpr (TAPE) {
+        float* tp = a.tape + lstm_tape_off(b, a.max_len, t, dir) + r;
+        tp[0] = ig; tp[128] = fg; tp[256] = gg; tp[384] = og; tp[512] = c;
+      }
     }
     __syncthreads();
   }
@@ -964,6 +973,7 @@ __global__ __launch_bounds__(512) void lstm_kernel(LstmArgs a) {
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x)); }
 __device__ __forceinline__ float fast_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008177792681f * x)); }
+template <bool TAPE = false>
 __global__ __launch_bounds__(512) void lstm_mfma_kernel(LstmArgs a, int n_seq) {
   GLAMR_CRITICAL_PATH_PRIO();
   constexpr int HS = 136;                                                   // halves per LDS row
@@ -1046,6 +1056,10 @@ __global__ __launch_bounds__(512) void lstm_mfma_kernel(LstmArgs a, int n_seq) {
         hnew = og * fast_tanh(c[r]);
         const int t = dir ? (len[r] - 1 - s) : s;
         Hb[r][(size_t)t * 256] = hnew;
+        if constexpr (TAPE) {
+          float* tp = a.tape + lstm_tape_off(s0 + m, a.max_len, t, dir) + u0 + n;      // (s < len[r] > 0: the sequence exists)
+          tp[0] = ig; tp[128] = fg; tp[256] = gg; tp[384] = og; tp[512] = c[r];
+        }
       }
       const _Float16 hh = (_Float16)hnew;
       sh[cur ^ 1][0][m][u0 + n] = hh;

@@ -269,6 +269,21 @@ class MotionInfillerVAE(_PriorBase):
         return data
 
 
+class _LocalTraj(torch.autograd.Function):
+    """TrajPredVAE.local_traj: the forward is glamr_nets_traj_taped, the backward glamr_nets_traj_backward (no arithmetic on the host)."""
+
+    @staticmethod
+    def forward(ctx, in_joint_pos, in_traj_latent, handle, lens):
+        out, tape = handle.traj_taped(lens, in_traj_latent.detach(), in_joint_pos=in_joint_pos.detach())
+        ctx.handle, ctx.tape = handle, tape
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        g_eps, g_joints = ctx.handle.traj_backward(ctx.tape, g, want_joints=ctx.needs_input_grad[0])
+        return g_joints, g_eps, None, None
+
+
 class TrajPredVAE(_PriorBase):
     LAYOUT = TRAJPRED_LAYOUT
     model_type = 'joint'
@@ -290,6 +305,15 @@ class TrajPredVAE(_PriorBase):
         return self._handle
 
     seq_len = 100            # chunk length of the multi-step (chunked) inference, traj_pred_demo.yml
+
+    def local_traj(self, in_joint_pos, in_traj_latent, lens=None):
+        """The predicted local trajectory (B,T,11) of inference mode as a DIFFERENTIABLE function of the joint rows in_joint_pos (B,T,69) and the
+        latent draw in_traj_latent (B,128); lens: frames per sequence (default: all T).  The reference detaches this output
+        (global_recon_model.py:396); here gradients reach both inputs through glamr_nets_traj_backward."""
+        h = self._ensure_handle()
+        B, T = in_joint_pos.shape[:2]
+        lens = [T] * B if lens is None else [int(n) for n in lens]
+        return _LocalTraj.apply(in_joint_pos, in_traj_latent, h, lens)
 
     def get_joint_pos(self, body_pose):
         """:384-394 -- forward kinematics of the 23 body joints for zero shape / root orientation, relative to the root."""

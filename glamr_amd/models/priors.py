@@ -158,6 +158,36 @@ class MotionPriorsHandle:
                                                 _lib.ptr(g_eps), _lib.ptr(tape['buf']), _lib.current_stream()))
         return g_eps
 
+    # -- the trajectory predictor, differentiable (glamr_nets_traj_taped / glamr_nets_traj_backward) --------------------------------------------
+    def traj_taped(self, lens, traj_eps, in_joint_pos=None, in_body_pose=None):
+        """The predictor of infer() / traj_clip(VAE_INFER) with what its backward needs kept: returns (out_local_traj (B,T,11), tape).
+        Exactly one of in_joint_pos / in_body_pose (B,T,69); traj_eps (B,128); lens list[int].  `tape` goes to traj_backward."""
+        L = _lib.lib()
+        if (in_joint_pos is None) == (in_body_pose is None):
+            raise ValueError('exactly one of in_joint_pos and in_body_pose must be given')
+        src = (in_joint_pos if in_joint_pos is not None else in_body_pose).float().contiguous()
+        B, T = src.shape[:2]
+        dev = src.device
+        traj_eps = traj_eps.float().contiguous()
+        lens_np = np.ascontiguousarray(lens, dtype=np.int32)
+        out = torch.empty((B, T, 11), device=dev)
+        buf = torch.empty(L.glamr_nets_traj_tape_bytes(self.h, B, T), dtype=torch.uint8, device=dev)
+        _lib.check(L.glamr_nets_traj_taped(self.h, B, T, _lib.ptr(lens_np), _lib.ptr(src) if in_joint_pos is not None else None,
+                                           _lib.ptr(src) if in_body_pose is not None else None, _lib.ptr(traj_eps), _lib.ptr(out), _lib.ptr(buf),
+                                           _lib.current_stream()))
+        return out, {'buf': buf, 'lens': lens_np, 'eps': traj_eps, 'B': B, 'T': T}
+
+    def traj_backward(self, tape, g_local_traj, want_joints=True):
+        """(dL/d traj_eps (B,128), dL/d joint rows (B,T,69) or None) for dL/d out_local_traj (B,T,11) of the taped call."""
+        L = _lib.lib()
+        eps = tape['eps']
+        g = g_local_traj.float().contiguous()
+        g_eps = torch.empty_like(eps)
+        g_joints = torch.empty((tape['B'], tape['T'], 69), device=eps.device) if want_joints else None
+        _lib.check(L.glamr_nets_traj_backward(self.h, tape['B'], tape['T'], _lib.ptr(tape['lens']), _lib.ptr(eps), _lib.ptr(g), _lib.ptr(g_eps),
+                                              _lib.ptr(g_joints), _lib.ptr(tape['buf']), _lib.current_stream()))
+        return g_eps, g_joints
+
     # -- training-mode / reconstruction passes (forward(data), inference(recon=True)) -----------------------------------------------------
     def infiller_window(self, mode, in_body_pose, frame_mask, eps=None, body_pose=None, want_context=True):
         """One 50-frame window per sequence through context encoder, (posterior encoder,) prior and decoder.  in_body_pose / body_pose

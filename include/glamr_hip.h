@@ -145,13 +145,33 @@ int glamr_nets_infer(glamr_nets* h, int n_seq, int max_len, const int32_t* lens,
  * glamr_nets_infill_backward then gives dL/d motion_eps (n_seq, n_win_max, 128) for a gradient g_out_pose (n_seq, max_len, 69) of the
  * generated body pose -- what torch autograd returns for `in_motion_latent` through MotionInfillerVAE.inference_multi_step (:618-632):
  * decoder, reparameterisation, prior and context encoder of every window and the autoregression between windows (:604-607).  Weights are
- * constants.  (The trajectory predictor needs no backward: get_pred_trajectory_base :396 detaches its output.)  lens / motion_eps must
- * be the ones of the taped call. */
+ * constants.  (The reference never differentiates the trajectory predictor: get_pred_trajectory_base :396 clones traj_local_pred after
+ * .detach(), so `traj_latent` keeps a gradient of None.  glamr_nets_traj_taped / glamr_nets_traj_backward below are the attached
+ * alternative.)  lens / motion_eps must be the ones of the taped call. */
 size_t glamr_nets_tape_bytes(const glamr_nets* h, int n_seq, int max_len);
 int glamr_nets_infill_taped(glamr_nets* h, int n_seq, int max_len, const int32_t* lens, const float* body_pose, const float* visible,
                             const float* motion_eps, int n_win_max, float* out_pose, void* tape, void* stream);
 int glamr_nets_infill_backward(glamr_nets* h, int n_seq, int max_len, const int32_t* lens, const float* motion_eps, int n_win_max,
                                const float* g_out_pose, float* g_motion_eps, void* tape, void* stream);
+
+/* The trajectory predictor, differentiable: the vector-Jacobian product of TrajPredVAE inference (traj_pred_vae.py:20-92, 202-334, 524-548),
+ * the map (joint-position rows, latent draw) -> infer_out_local_traj_tp, weights constant.  glamr_nets_traj_taped is the predictor of
+ * glamr_nets_infer / glamr_nets_traj_clip(GLAMR_VAE_INFER) -- the same kernels on the same route, out_local_traj (n_seq, max_len, 11) bit for
+ * bit -- with its activations and every recurrence step's gates and cell state kept in `tape` (glamr_nets_traj_tape_bytes: ~25 KB per frame
+ * and sequence, values + gradients).  Exactly one of in_joint_pos (n_seq, max_len, 69: the rows the context encoder reads) and in_body_pose
+ * (n_seq, max_len, 69: joints by the forward-kinematics kernel) is given; lens[b] in [1, max_len].  glamr_nets_traj_backward then gives, for
+ * an upstream gradient g_local_traj (n_seq, max_len, 11), g_eps (n_seq, 128) = dL/d traj_eps and g_joint_pos (n_seq, max_len, 69; may be NULL)
+ * = dL/d the joint rows (also after in_body_pose: the FK backward is not part of it) through decoder, reparameterisation, prior (the mean over
+ * a sequence's own frames) and context encoder (out_mlp, two bi-LSTM layers by BPTT, in_mlp).  Row 0, columns 0, 1, 9, 10 of the output are
+ * constants (:319-327): their upstream entries contribute nothing; rows at or beyond lens[b] of g_joint_pos are zero.  Two calls give the same
+ * bits; the result does not depend on the magnitude of g_local_traj (gradient rows are scaled by powers of two around the fp16 products).
+ * lens / traj_eps must be the ones of the taped call.  All work goes on `stream`; the transposed weights are made once per handle by the
+ * first glamr_nets_traj_taped. */
+size_t glamr_nets_traj_tape_bytes(const glamr_nets* h, int n_seq, int max_len);
+int glamr_nets_traj_taped(glamr_nets* h, int n_seq, int max_len, const int32_t* lens, const float* in_joint_pos, const float* in_body_pose,
+                          const float* traj_eps, float* out_local_traj, void* tape, void* stream);
+int glamr_nets_traj_backward(glamr_nets* h, int n_seq, int max_len, const int32_t* lens, const float* traj_eps, const float* g_local_traj,
+                             float* g_eps, float* g_joint_pos, void* tape, void* stream);
 
 /* Training-mode / reconstruction passes of the two VAEs -- what `forward(data)` and `inference(recon=True)` run:
  *   MotionInfillerVAE.forward  motion_infiller/models/motion_infiller_vae.py:478-482 = ContextEncoder :92-123, DataEncoder (posterior)
