@@ -26,7 +26,7 @@ class SceneBatch(Structure):
                [(n, c_void_p) for n in ('n_persons', 'seq_len', 'fr_start', 'fr_end', 'vis', 'j_local', 'kp_2d', 'kp_score', 'cam_K',
                                         'traj_local_pred', 'orient_cam', 'base_orient', 'base_trans', 'person2cam', 'dheading_mask',
                                         'rel_transform_cam', 'cam_pose', 'params', 'losses', 'orient_world', 'trans_world',
-                                        'kp_2d_pred', 'orient_cam_in_world', 'frozen', 'g_j_local', 'loss_history')]
+                                        'kp_2d_pred', 'orient_cam_in_world', 'frozen', 'g_j_local', 'g_traj_local', 'loss_history')]
 
 
 class FilterOpts(Structure):
@@ -82,6 +82,7 @@ _SIGNATURES = {
     'glamr_nets_traj_tape_bytes': (c_size_t, [c_void_p, c_int, c_int]),
     'glamr_nets_traj_taped': (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 7),
     'glamr_nets_traj_backward': (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 7),
+    'glamr_nets_fk_backward': (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 5),
     'glamr_nets_infer': (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 5 + [c_int, c_void_p, c_void_p]),
     'glamr_nets_infiller_window': (c_int, [c_void_p, c_int, c_int, POINTER(InfillerIO), c_void_p, c_void_p]),
     'glamr_nets_traj_clip': (c_int, [c_void_p, c_int, c_int, c_int, POINTER(TrajIO), c_void_p, c_void_p]),

@@ -68,6 +68,32 @@ __global__ __launch_bounds__(MAX_THREADS, WAVES_PER_EU) void grecon_stage_kernel
   if (threadIdx.x == 0) atomicMax(a.stamps + 1, (unsigned long long)wall_clock64());
 }
 
+// The instances of a launch that also asks for dL/d traj_local_pred (glamr_scene_batch.g_traj_local: the attached trajectory prior of the
+// latent-optimisation mode).  A kernel of its own, so that the instances above -- their names included -- are what they were.
+template <int FAST>
+__global__ __launch_bounds__(MAX_THREADS, WAVES_PER_EU) void grecon_stage_traj_grad_kernel(KernelArgs a) {
+  __shared__ __attribute__((aligned(16))) float red[RT_RED_FLOATS];
+  __shared__ Scene sc;
+  __shared__ glamr_stage_desc s_st;
+  __shared__ glamr_param_layout s_lay;
+  extern __shared__ __attribute__((aligned(16))) float arena[];
+  const int si = blockIdx.x;
+  __builtin_amdgcn_s_setprio(3);
+  if (threadIdx.x == 0) {
+    atomicMin(a.stamps, (unsigned long long)wall_clock64());
+    s_st = a.st;
+    s_lay = a.lay;
+    assemble_scene(a.b, s_lay, &s_st, si, a.b.n_persons[si], a.b.seq_len[si], a.workspace + (size_t)si * a.ws_floats_per_scene, a.grads_out, sc,
+                   a.use_lds ? arena : nullptr, a.fast_floats, a.use_lds, a.layout_len);
+    sc.adam_tab = a.adam_tab;
+  }
+  __syncthreads();
+  glamr::DeviceRT rt{red, a.workspace + (size_t)si * a.ws_floats_per_scene};
+  const TrajGradOut gt{a.b.g_traj_local + (size_t)si * a.b.max_persons * a.b.max_len * 11, a.b.max_persons, a.b.max_len};
+  run_scene<FAST, false, 0, 0, true>(rt, sc, a.st, a.lay, gt);
+  if (threadIdx.x == 0) atomicMax(a.stamps + 1, (unsigned long long)wall_clock64());
+}
+
 }  // namespace GLAMR_GRECON_NS
 }  // namespace glamr
 
@@ -156,6 +182,8 @@ extern "C" int glamr_grecon_run_stage(const glamr_scene_batch* batch, const glam
   GLAMR_REQUIRE(batch->max_persons == 1 || batch->rel_transform_cam || !((stage->loss_mask >> GLAMR_LOSS_REL_TRANSFORM) & 1u),
                 "rel_transform loss needs rel_transform_cam for multi-person scenes");
   GLAMR_REQUIRE(stage->niters >= 0, "niters must be >= 0");
+  GLAMR_REQUIRE(!batch->g_traj_local || (grads_out && stage->niters >= 1 && !(stage->flags & GLAMR_FLAG_ABSOLUTE_HEADING) && !(batch->loss_history)),
+                "g_traj_local needs grads_out and niters >= 1, and goes with neither absolute headings nor the loss history");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   KernelArgs ka;
   ka.b = *batch;
@@ -257,6 +285,14 @@ extern "C" int glamr_grecon_run_stage(const glamr_scene_batch* batch, const glam
     return GLAMR_OK;
   };
   int rc;
+  if (batch->g_traj_local) {
+    // the general instance (several persons, any camera mode) on the lite arena, or in the workspace: one pair per compile
+    ka.use_lds = lite <= LDS_BUDGET ? 2 : 0;
+    const size_t want2 = lite + (size_t)NJ * 6 * batch->max_persons * batch->max_len * sizeof(float);
+    ka.fast_floats = (unsigned)((ka.use_lds ? (want2 < LDS_BUDGET ? want2 : LDS_BUDGET) : 0) / sizeof(float));
+    ka.layout_len = 0;
+    rc = ka.use_lds == 2 ? launch(grecon_stage_traj_grad_kernel<2>, (size_t)ka.fast_floats * sizeof(float)) : launch(grecon_stage_traj_grad_kernel<0>, 0);
+  } else {
 #ifdef GLAMR_GRECON_WIDE
   if (ka.use_lds == 1 || ka.use_lds == 3 || ka.use_lds == 4) {      // (the full arena of > 8 persons never fits; kept from being instantiated -- the mid arena likewise)
     ka.use_lds = lite <= LDS_BUDGET ? 2 : 0;
@@ -285,6 +321,7 @@ extern "C" int glamr_grecon_run_stage(const glamr_scene_batch* batch, const glam
   else
     rc = launch(grecon_stage_kernel<0, false, 0>, 0);
 #endif
+  }
   if (rc) return rc;
   GLAMR_HIP_CHECK(hipGetLastError());
 #ifndef GLAMR_GRECON_WIDE

@@ -784,8 +784,14 @@ GLAMR_HD void copy_person_block(RT& rt, float* dst, const glamr_param_layout& ld
 // TMC > 0: constant-layout instance (see the view builders): arena / workspace arrays laid out for TMC frames, on-chip parameter blocks in
 // the parameter layout of TMC frames (`lo`; the batch arrays keep the batch's own layout `l`).
 template <int TMC> struct OnChipLayout { static constexpr glamr_param_layout value = make_layout(1, TMC > 0 ? TMC : 2); };
-template <int FAST, bool SINGLE, int CAM, int TMC = 0, class RT>
-GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const glamr_param_layout& l) {
+// GT: the instance also writes dL/d traj_local_pred of the scene's persons (glamr_scene_batch.g_traj_local) -- `gt.base` = the scene's first
+// person slot, [max_persons][max_len][11].  Only the launches that ask for it run GT instances; every other instance is compiled without a
+// trace of it (the stores, their address arithmetic and the pointer are template-dependent, and the scene description is not touched).
+struct TrajGradOut { float* base; int max_persons, max_len; };      // (the two in glamr_scene_batch's order: copied as a pair)
+template <int FAST, bool SINGLE, int CAM, int TMC = 0, bool GT = false, class RT>
+GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const glamr_param_layout& l, TrajGradOut gt = TrajGradOut{nullptr, 0, 0}) {
+  static_assert(!GT || TMC == 0, "the trajectory-row gradient is not written by the constant-layout instances");
+  [[maybe_unused]] auto gt_row = [&](int p, int e) { return glob(gt.base) + ((size_t)p * gt.max_len + e) * 11; };
   constexpr bool AF = FAST == 1 && SINGLE;          // parameters + Adam moments on chip (assemble_scene: adam_fast)
   static_assert(TMC == 0 || AF, "constant layouts are for single-person scenes with the full arena");
   const glamr_param_layout& lo = TMC > 0 ? OnChipLayout<TMC>::value : l;      // layout of the on-chip parameter / moment blocks
@@ -1679,6 +1685,11 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
           for (int r = 0; r < 3; ++r) { gRl[r * 3 + 0] = 0.f; gRl[r * 3 + 1] = gb2[r]; gRl[r * 3 + 2] = gb3[r]; }
           rm::rot6d_to_rotmat_bwd(L.r6, gRl, gr6);
         }
+        if constexpr (GT) {      // columns 2-8 of dL/d traj_local_pred: the row's data-term gradient, before the regularisers of the deltas
+          float* o = gt_row(p, e);
+          o[2] = s.g_tw[t * 3 + 2];
+          for (int k = 0; k < 6; ++k) o[3 + k] = gr6[k];
+        }
         if (REG_ANY) { gth_r[0] = gth; gxy_r[0] = s.g_tw[t * 3 + 0]; gxy_r[1] = s.g_tw[t * 3 + 1]; } else {
           s.g_theta[t] = gth;
           s.g_xy[t * 2 + 0] = s.g_tw[t * 3 + 0];
@@ -1755,6 +1766,7 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
             gx = a; gy = b;
           }
           const float g[2] = {gx, gy};
+          if constexpr (GT) { float* o = gt_row(p, e); o[0] = gx; o[1] = gy; }      // columns 0-1
           {
             float g2[2];
             for (int k = 0; k < 2; ++k) {
@@ -1815,6 +1827,13 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
           AdamRegs<1> a_h = a_hpre;
           if (!REG_ANY) { if (upd) a_h.load(s.p, s.m, s.v, i); else a_h.P[0] = s.p[i]; }
           float gj[1] = {gh};
+          if constexpr (GT) {      // columns 9-10: the heading angle's gradient (no dheading_mask: it multiplies the delta) through vec_to_heading at the prior row
+            float* o = gt_row(p, e);
+            const float* pr = c.prior + (size_t)e * 11;
+            float gy = 0.f, gx = 0.f;
+            rm::atan2s_bwd(pr[10], pr[9], gh, gy, gx);
+            o[9] = gx; o[10] = gy;
+          }
           if (!first) {
             const float v = a_h.P[0];
             float sv, cv;
@@ -1826,6 +1845,12 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
           }
           if (upd) a_h.step_store(s.p, s.m, s.v, sh.store_grad ? s.g : nullptr, i, gj, ac);
         }
+    }
+    if constexpr (GT) {      // rows beyond a person's frames and the scene's empty slots
+      for (int p = 0; p < gt.max_persons; ++p) {
+        const int n = p < P ? pv(p).fr_end - pv(p).fr_start : 0;
+        for (int e = n + rt.tid(); e < gt.max_len; e += rt.nthreads()) { float* o = gt_row(p, e); for (int k = 0; k < 11; ++k) o[k] = 0.f; }
+      }
     }
     // regulariser values that do not depend on being optimised (reported every evaluation)
     if (last) {

@@ -171,6 +171,7 @@ struct glamr_nets {
   bool fp32_only = false;
   double worst_activation = 0, worst_weight = 0;
   std::map<const Lin*, Lin> lin_T;      // transposed weights of the layers the infiller's backward multiplies with (nets_tape.hpp), made on first use
+  int* fk_lens = nullptr; int fk_lens_cap = 0;      // device copy of the lengths of glamr_nets_fk_backward (the call has no workspace); grown outside captures
 };
 constexpr size_t GRAPH_CACHE_MAX = 24, CAPTURE_LENS_INTS = 256 * 1024;
 
@@ -276,6 +277,72 @@ __global__ __launch_bounds__(256) void fk_joints_kernel(const float* pose, int T
   if (!active) { for (int c = j * 4; c < j * 4 + 4; ++c) xo[c] = 0.0f; return; }      // 24 threads x 4 columns = the 96 of a padded row
   if (j > 0) for (int c = 0; c < 3; ++c) xo[(j - 1) * 3 + c] = sP[fl][j][c] - sP[fl][0][c];
   else for (int c = 69; c < XLD; ++c) xo[c] = 0.0f;
+}
+// The vector-Jacobian product of fk_joints_kernel: dL/d joint rows [B][max_len][69] -> dL/d body pose [B][max_len][69].  The chain is
+// recomputed from the pose (same geometry: a thread per (frame, joint), FK_FRAMES frames per workgroup).  A joint's rotation moves every
+// descendant: the gradients of the global rotations and positions travel from the leaves up, one tree level per barrier, each PARENT adding
+// its children's contributions in joint order (one writer per entry, a fixed order of additions: two calls give the same bits).
+//   P_j = P_pa + G_pa d_j,  G_j = G_pa R_j,  x_j = P_j - P_0:   gP_pa += gP_j,  gG_pa += gP_j d_j^T + gG_j R_j^T,  gR_j = G_pa^T gG_j
+__global__ __launch_bounds__(256) void fk_joints_bwd_kernel(const float* body_pose, const float* gx, int max_len, const int* lens, const float* rest,
+                                                            const int32_t* parents, float* g_pose) {
+  __shared__ float sG[FK_FRAMES][24][9], sR[FK_FRAMES][24][9], sgG[FK_FRAMES][24][9], sgP[FK_FRAMES][24][3];
+  __shared__ int sLev[24];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int fl = tid / 24, j = tid % 24;
+  const int t = blockIdx.y * FK_FRAMES + fl;
+  if (tid < 24) {
+    int lev = 0;
+    for (int a = parents[tid]; a >= 0; a = parents[a]) ++lev;
+    sLev[tid] = lev;
+  }
+  __syncthreads();
+  int nlev = 0;
+  for (int k = 0; k < 24; ++k) nlev = sLev[k] > nlev ? sLev[k] : nlev;
+  const bool active = fl < FK_FRAMES && t < max_len && t < lens[b];
+  const int pa = parents[j], lev = sLev[j];
+  const size_t row = ((size_t)b * max_len + t) * 69;
+  float aa[3] = {0.f, 0.f, 0.f};
+  if (active) {
+    if (j > 0) for (int c = 0; c < 3; ++c) aa[c] = body_pose[row + (j - 1) * 3 + c];
+    float R[9];
+    rm::aa_to_rotmat_s(aa, R);                      // (root: rodrigues of the zero vector, as in the forward)
+    for (int e = 0; e < 9; ++e) { sR[fl][j][e] = R[e]; sgG[fl][j][e] = 0.f; }
+    if (j == 0) for (int e = 0; e < 9; ++e) sG[fl][0][e] = R[e];
+    for (int c = 0; c < 3; ++c) sgP[fl][j][c] = j > 0 ? gx[row + (j - 1) * 3 + c] : 0.f;
+  }
+  __syncthreads();
+  for (int L = 1; L <= nlev; ++L) {                 // global rotations, root to leaves
+    if (active && lev == L) {
+      float G[9];
+      rm::mat3_mul(sG[fl][pa], sR[fl][j], G);
+      for (int e = 0; e < 9; ++e) sG[fl][j][e] = G[e];
+    }
+    __syncthreads();
+  }
+  for (int L = nlev - 1; L >= 1; --L) {             // gradients, leaves to root (the root's own rotation and position are constants)
+    if (active && lev == L) {
+      float gG[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, gP[3] = {sgP[fl][j][0], sgP[fl][j][1], sgP[fl][j][2]};
+      for (int c = 0; c < 24; ++c) {
+        if (parents[c] != j) continue;
+        const float d[3] = {rest[c * 3] - rest[j * 3], rest[c * 3 + 1] - rest[j * 3 + 1], rest[c * 3 + 2] - rest[j * 3 + 2]};
+        const float* gPc = sgP[fl][c];
+        for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) gG[r * 3 + k] += gPc[r] * d[k];
+        rm::mat3_mul_bwd(sG[fl][j], sR[fl][c], sgG[fl][c], gG, nullptr);      // gG += gG_c R_c^T
+        for (int r = 0; r < 3; ++r) gP[r] += gPc[r];
+      }
+      for (int e = 0; e < 9; ++e) sgG[fl][j][e] = gG[e];
+      for (int r = 0; r < 3; ++r) sgP[fl][j][r] = gP[r];
+    }
+    __syncthreads();
+  }
+  if (fl >= FK_FRAMES || t >= max_len || j == 0) return;
+  float g[3] = {0.f, 0.f, 0.f};
+  if (active) {
+    float gR[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    rm::mat3_mul_bwd(sG[fl][pa], sR[fl][j], sgG[fl][j], nullptr, gR);         // gR_j = G_pa^T gG_j
+    rm::aa_to_rotmat_s_bwd(aa, gR, g);
+  }
+  for (int c = 0; c < 3; ++c) g_pose[row + (j - 1) * 3 + c] = g[c];
 }
 __global__ void masked_mean_kernel(const float* ctx, int max_len, const int* lens, float* mean, int frag = 0) {   // [B][max_len][256] -> [B][256]
   const int b = blockIdx.x, n = lens[b];
@@ -1469,6 +1536,32 @@ extern "C" int glamr_nets_traj_backward(glamr_nets* h, int B, int max_len, const
   hipStream_t st = static_cast<hipStream_t>(stream_);
   const TrajTape t = traj_tape_layout(B, max_len, static_cast<char*>(tape_));
   RC(traj_backward_pass(h, Plan{st, h->fp32_only, false, true}, t, B, max_len, traj_eps, g_local_traj, g_eps, g_joint_pos));
+  GLAMR_HIP_CHECK(hipGetLastError());
+  return GLAMR_OK;
+}
+
+// The VJP of the forward-kinematics step between body pose and the predictor's joint rows (fk_joints_kernel): g_joint_pos (n_seq, max_len, 69)
+// -> g_body_pose (n_seq, max_len, 69), the chain recomputed from body_pose; rows at or beyond lens[b] are zero.
+extern "C" int glamr_nets_fk_backward(glamr_nets* h, int B, int max_len, const int32_t* lens_host, const float* body_pose, const float* g_joint_pos,
+                                      float* g_body_pose, void* stream_) {
+  GLAMR_REQUIRE(h && lens_host && body_pose && g_joint_pos && g_body_pose, "null argument");
+  GLAMR_REQUIRE(B > 0 && max_len > 0, "need n_seq > 0 and max_len > 0");
+  RC(check_traj_lens(lens_host, B, max_len));
+  hipStream_t st = static_cast<hipStream_t>(stream_);
+  if (B > h->fk_lens_cap) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    GLAMR_REQUIRE(!(st && hipStreamIsCapturing(st, &cap) == hipSuccess && cap == hipStreamCaptureStatusActive),
+                  "the first glamr_nets_fk_backward call of %d sequences must not be recorded into a graph (it allocates the lengths' device copy)", B);
+    const int n = B > 2 * h->fk_lens_cap ? B : 2 * h->fk_lens_cap;
+    int* p = nullptr;
+    GLAMR_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&p), (size_t)n * sizeof(int)));
+    h->allocs.push_back(p);                          // (the smaller one may still be read by enqueued work: both live until glamr_nets_destroy)
+    h->fk_lens = p; h->fk_lens_cap = n;
+  }
+  bool capturing = false;
+  RC(stage_lens(h, st, lens_host, B, h->fk_lens, false, &capturing));
+  hipLaunchKernelGGL(fk_joints_bwd_kernel, dim3(B, (max_len + FK_FRAMES - 1) / FK_FRAMES), dim3(256), 0, st, body_pose, g_joint_pos, max_len, h->fk_lens,
+                     h->rest_joints, h->parents, g_body_pose);
   GLAMR_HIP_CHECK(hipGetLastError());
   return GLAMR_OK;
 }

@@ -251,6 +251,12 @@ class GlobalReconOptimizer:
         # latent-optimisation mode (:43-44,155-158,434-437,619-622): the priors run INSIDE the Adam loop and the latent draws are parameters
         self.flag_opt_motion_latent = bool(g('flag_opt_motion_latent', False))
         self.flag_opt_traj_latent = bool(g('flag_opt_traj_latent', False))
+        # flag_attach_traj_pred (NOT a reference key): the latent-optimisation mode with the trajectory prior ATTACHED -- what the reference would
+        # compute with the .detach() of :396 removed.  `traj_latent` then receives a gradient (and moves, with flag_opt_traj_latent), and
+        # `motion_latent` also the term infiller -> body pose -> FK joints -> predictor -> trajectory.  Off: the reference's behaviour, to the bit.
+        self.flag_attach_traj_pred = bool(g('flag_attach_traj_pred', False))
+        if self.flag_attach_traj_pred and not (self.flag_opt_motion_latent or self.flag_opt_traj_latent):
+            raise ValueError('flag_attach_traj_pred needs the latent-optimisation mode (flag_opt_motion_latent and / or flag_opt_traj_latent)')
         self.flag_filter_pose = g('flag_filter_pose', True)
         # keypoint-count filter inside filter_pose (:50-52,264-268); with HybrIK's binary scores (14 scored joints per detected frame) it is all or
         # nothing: the reference's default minimum of 15 removes every frame, 14 or less none
@@ -1188,9 +1194,10 @@ class GlobalReconOptimizer:
         meps, teps = meps.clone(), teps.clone()
         pa = packed.person_arrays
         h = self.mt_model.handle
-        tape_gb = L.glamr_nets_tape_bytes(h.h, n_slots, T) / 2.0 ** 30
+        attach = self.flag_attach_traj_pred
+        tape_gb = (L.glamr_nets_tape_bytes(h.h, n_slots, T) + (L.glamr_nets_traj_tape_bytes(h.h, n_slots, T) if attach else 0)) / 2.0 ** 30
         if tape_gb > 96:
-            raise ValueError('latent-optimisation mode keeps every activation of the infiller for its backward: %.0f GB for %d person slots of %d frames; '
+            raise ValueError('latent-optimisation mode keeps every activation of the infiller (and of the attached trajectory predictor) for its backward: %.0f GB for %d person slots of %d frames; '
                              'run it on smaller batches (the reference runs it on one sequence at a time)' % (tape_gb, n_slots, T))
         lens = np.ascontiguousarray(rin.lens, dtype=np.int32)
         fr_start = packed.t['fr_start'].cpu().numpy()
@@ -1208,10 +1215,17 @@ class GlobalReconOptimizer:
         smpl_h = self.smpl._handle(dev)
         zeros3 = torch.zeros((n_slots * T, 3), device=dev)
         packed.t['g_j_local'] = torch.zeros((n_slots, T, packing.NJ, 3), device=dev)
+        if attach:
+            # dL/d traj_local_pred of the gradient launch, rows in the priors' own order (traj_local_pred is stored by existing-frame row);
+            # the predictor takes lengths >= 1: an empty slot runs as one frame whose gradient rows are zero
+            g_traj_local = torch.zeros((n_slots, T, 11), device=dev)
+            lens_t = np.maximum(lens, 1).astype(np.int32)
         params = packed.t['params']
         m_lat, v_lat = torch.zeros_like(meps), torch.zeros_like(meps)
+        m_tl, v_tl = torch.zeros_like(teps), torch.zeros_like(teps)      # traj_latent's own moments (attached mode only)
+        extra = {}
         m, v = torch.zeros_like(params), torch.zeros_like(params)
-        step_idx = torch.zeros(2, dtype=torch.int32, device=dev)         # [0] scene parameters, [1] latents: 0-based row of the coefficient table
+        step_idx = torch.zeros(3, dtype=torch.int32, device=dev)         # [0] scene parameters, [1] motion latents, [2] trajectory latents: 0-based row of the coefficient table
         has_wd = False
         use_graph = os.environ.get('GLAMR_LATENT_GRAPH', '1') != '0'
         self.latent_graph_replays = 0
@@ -1219,11 +1233,15 @@ class GlobalReconOptimizer:
         def iteration(spec, with_priors, first, coef):
             """One Adam iteration (:547-570 in latent mode), launches only -- nothing here reads a value back or depends on the iteration
             number except through `step_idx` on the device, so the same launch sequence is captured ONCE per stage and replayed."""
-            tape = None
+            tape = ttape = None
             if with_priors:
                 # infer_motion_traj with the current latents (:352-392)
                 pose_out, tape = h.infill_taped(pa['nets_pose'], pa['nets_vis'], lens, meps)
-                tr = h.infer(pose_out, None, lens, traj_eps=teps, infill=False, traj=True)
+                if attach:      # the same predictor with its activations kept (the rows are bit-identical, DESIGN.md 11)
+                    local_traj, ttape = h.traj_taped(lens_t, teps, in_body_pose=pose_out)
+                    tr = {'local_traj': local_traj}
+                else:
+                    tr = h.infer(pose_out, None, lens, traj_eps=teps, infill=False, traj=True)
                 pa['smpl_pose'].view(-1, 69).index_copy_(0, dst, pose_out.view(-1, 69).index_select(0, src))
                 packed.t['traj_local_pred'].view(-1, 11).index_copy_(0, src, tr['local_traj'].view(-1, 11).index_select(0, src))
                 with torch.no_grad():
@@ -1237,8 +1255,20 @@ class GlobalReconOptimizer:
             sd.lr = 0.0
             if not first:
                 sd.flags |= packing.FLAG_KEEP_CAM_PARAMS
+            # (only a launch whose priors ran has a reader for dL/d traj_local_pred: before opt_latent_start_iter the usual instance runs)
+            packed.t['g_traj_local'] = g_traj_local if ttape is not None else None
             grads = parallel._device_run_stage(packed, sd, True)
-            g_lat = None
+            g_lat = g_bp = None
+            if ttape is not None:
+                # dL/d traj_local_pred -> trajectory latent, and -> joint rows -> body pose (the FK step in reverse) for the motion latent
+                g_tl, g_joints = h.traj_backward(ttape, g_traj_local, want_joints=self.flag_opt_motion_latent)
+                extra['g_traj_latent'] = g_tl
+                if g_joints is not None:
+                    g_bp = h.fk_backward(pose_out, lens_t, g_joints)
+                if self.flag_opt_traj_latent:
+                    _lib.check(L.glamr_adam_step_indexed(teps.numel(), _lib.ptr(teps), _lib.ptr(m_tl), _lib.ptr(v_tl), _lib.ptr(g_tl), _lib.ptr(coef), _lib.ptr(step_idx[2:]),
+                                                         _lib.current_stream()))
+                    _lib.check(L.glamr_counter_add(_lib.ptr(step_idx[2:]), 1, _lib.current_stream()))
             if tape is not None and self.flag_opt_motion_latent:
                 # dL/d j_local -> body pose (skinning, blend shapes, chain, re-anchoring in reverse) -> latents (all windows)
                 pose72 = torch.cat([zeros3, pa['smpl_pose'].view(-1, 69)], dim=1).contiguous()
@@ -1248,6 +1278,8 @@ class GlobalReconOptimizer:
                                                  None, _lib.ptr(packed.t['g_j_local']), _lib.ptr(g_pose), None, None, None, 0, _lib.ptr(ws), _lib.current_stream()))
                 g_out = torch.zeros((n_slots * T, 69), device=dev)
                 g_out.index_copy_(0, src, g_pose[:, 3:].index_select(0, dst))
+                if g_bp is not None:
+                    g_out += g_bp.view(-1, 69)
                 g_lat = h.infill_backward(tape, g_out.view(n_slots, T, 69))
                 # (a parameter's step count advances only when it has a gradient: the latents have their own index)
                 _lib.check(L.glamr_adam_step_indexed(meps.numel(), _lib.ptr(meps), _lib.ptr(m_lat), _lib.ptr(v_lat), _lib.ptr(g_lat), _lib.ptr(coef), _lib.ptr(step_idx[1:]),
@@ -1262,7 +1294,7 @@ class GlobalReconOptimizer:
             n = spec['opt_niters'] if max_iters is None else min(max_iters, spec['opt_niters'])
             start = spec.get('opt_latent_start_iter', 0)                 # optimize() :581
             # init_opt creates a fresh optimiser per stage (:635-644): zero moments, step counts back to the first row of the stage's table
-            m.zero_(); v.zero_(); m_lat.zero_(); v_lat.zero_(); step_idx.zero_()
+            m.zero_(); v.zero_(); m_lat.zero_(); v_lat.zero_(); m_tl.zero_(); v_tl.zero_(); step_idx.zero_()
             tab = np.empty(2 * max(n, 1), np.float32)
             _lib.check(L.glamr_adam_coef_table(float(spec['opt_lr']), max(n, 1), tab.ctypes.data_as(ctypes.c_void_p)))
             coef = torch.as_tensor(tab, device=dev)
@@ -1274,9 +1306,14 @@ class GlobalReconOptimizer:
                     self.latent_graph_replays += 1
                     continue
                 g_lat = iteration(spec, with_priors, it == 0, coef)
-                if g_lat is not None and getattr(self, 'latent_trace', None) is not None and not self.latent_trace:      # first gradient of the run, for the parity tests
-                    self.latent_trace.update(g_motion_latent=g_lat.detach().cpu().numpy(), losses=packed.t['losses'].detach().cpu().numpy(),
+                if (g_lat is not None or (with_priors and attach)) and getattr(self, 'latent_trace', None) is not None and not self.latent_trace:      # first gradient of the run, for the parity tests
+                    self.latent_trace.update(losses=packed.t['losses'].detach().cpu().numpy(),
                                              smpl_pose=pa['smpl_pose'].detach().cpu().numpy(), traj_local_pred=packed.t['traj_local_pred'].detach().cpu().numpy())
+                    if g_lat is not None:
+                        self.latent_trace['g_motion_latent'] = g_lat.detach().cpu().numpy()
+                    if attach:
+                        self.latent_trace.update(g_traj_latent=extra['g_traj_latent'].detach().cpu().numpy(),
+                                                 g_traj_local=g_traj_local.detach().cpu().numpy())
                 # from here on every iteration of the stage is the same launch sequence: capture it once, replay it n - it - 2 times
                 if use_graph and with_priors and it >= 1 and n - it - 1 >= 2 and not torch.cuda.is_current_stream_capturing():
                     try:
@@ -1301,6 +1338,7 @@ class GlobalReconOptimizer:
         packed.stage_ws = []
         packed.latents = (meps, teps)
         packed.t['g_j_local'] = None
+        packed.t['g_traj_local'] = None
         return packed
 
     def collect(self, datas, packed, fetched=None):

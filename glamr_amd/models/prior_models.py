@@ -284,6 +284,21 @@ class _LocalTraj(torch.autograd.Function):
         return g_joints, g_eps, None, None
 
 
+class _JointPos(torch.autograd.Function):
+    """TrajPredVAE.joint_pos: the forward is get_joint_pos, the backward glamr_nets_fk_backward (no arithmetic on the host)."""
+
+    @staticmethod
+    def forward(ctx, body_pose, model, lens):
+        ctx.handle, ctx.lens = model._ensure_handle(), lens
+        ctx.save_for_backward(body_pose.detach())
+        return model.get_joint_pos(body_pose.detach())
+
+    @staticmethod
+    def backward(ctx, g):
+        (body_pose,) = ctx.saved_tensors
+        return ctx.handle.fk_backward(body_pose, ctx.lens, g), None, None
+
+
 class TrajPredVAE(_PriorBase):
     LAYOUT = TRAJPRED_LAYOUT
     model_type = 'joint'
@@ -314,6 +329,14 @@ class TrajPredVAE(_PriorBase):
         B, T = in_joint_pos.shape[:2]
         lens = [T] * B if lens is None else [int(n) for n in lens]
         return _LocalTraj.apply(in_joint_pos, in_traj_latent, h, lens)
+
+    def joint_pos(self, body_pose, lens=None):
+        """get_joint_pos as a DIFFERENTIABLE function of body_pose (B,T,69): the joint rows (B,T,69) the predictor reads, so that
+        local_traj(joint_pos(pose), eps) backpropagates to `pose` under torch autograd.  lens: frames per sequence (default: all T); the
+        gradient of rows at or beyond a sequence's length is zero."""
+        B, T = body_pose.shape[:2]
+        lens = [T] * B if lens is None else [int(n) for n in lens]
+        return _JointPos.apply(body_pose.to(self.device).float(), self, lens)
 
     def get_joint_pos(self, body_pose):
         """:384-394 -- forward kinematics of the 23 body joints for zero shape / root orientation, relative to the root."""

@@ -188,6 +188,17 @@ class MotionPriorsHandle:
                                               _lib.ptr(g_joints), _lib.ptr(tape['buf']), _lib.current_stream()))
         return g_eps, g_joints
 
+    def fk_backward(self, body_pose, lens, g_joint_pos):
+        """dL/d body_pose (B,T,69) for dL/d joint rows (B,T,69) of the predictor's forward-kinematics step (glamr_nets_fk_backward): the chain is
+        recomputed from body_pose; rows at or beyond lens[b] are zero."""
+        L = _lib.lib()
+        body_pose, g_joint_pos = body_pose.float().contiguous(), g_joint_pos.float().contiguous()
+        B, T = body_pose.shape[:2]
+        lens_np = np.ascontiguousarray(lens, dtype=np.int32)
+        g_pose = torch.empty((B, T, 69), device=body_pose.device)
+        _lib.check(L.glamr_nets_fk_backward(self.h, B, T, _lib.ptr(lens_np), _lib.ptr(body_pose), _lib.ptr(g_joint_pos), _lib.ptr(g_pose), _lib.current_stream()))
+        return g_pose
+
     # -- training-mode / reconstruction passes (forward(data), inference(recon=True)) -----------------------------------------------------
     def infiller_window(self, mode, in_body_pose, frame_mask, eps=None, body_pose=None, want_context=True):
         """One 50-frame window per sequence through context encoder, (posterior encoder,) prior and decoder.  in_body_pose / body_pose

@@ -173,6 +173,16 @@ int glamr_nets_traj_taped(glamr_nets* h, int n_seq, int max_len, const int32_t* 
 int glamr_nets_traj_backward(glamr_nets* h, int n_seq, int max_len, const int32_t* lens, const float* traj_eps, const float* g_local_traj,
                              float* g_eps, float* g_joint_pos, void* tape, void* stream);
 
+/* The vector-Jacobian product of the forward-kinematics step between body pose and the predictor's joint rows (TrajPredVAE.get_joint_pos
+ * traj_pred_vae.py:384-394 -> SMPL.get_joints: zero root orientation, unshaped template, the rest joints and parents of glamr_nets_create,
+ * Rodrigues with smplx's epsilon convention): g_joint_pos (n_seq, max_len, 69) -> g_body_pose (n_seq, max_len, 69).  The chain is recomputed
+ * from body_pose (n_seq, max_len, 69): no tape.  A joint's rotation moves every descendant; contributions are added from the leaves up, one
+ * tree level at a time, in a fixed order: two calls give the same bits.  Rows at or beyond lens[b] (host, in [1, max_len]) are zero.  The
+ * handle keeps the device copy of `lens`: calls of one handle must be ordered by their streams, and the first call with more sequences than
+ * any before allocates and cannot be recorded into a graph. */
+int glamr_nets_fk_backward(glamr_nets* h, int n_seq, int max_len, const int32_t* lens, const float* body_pose, const float* g_joint_pos,
+                           float* g_body_pose, void* stream);
+
 /* Training-mode / reconstruction passes of the two VAEs -- what `forward(data)` and `inference(recon=True)` run:
  *   MotionInfillerVAE.forward  motion_infiller/models/motion_infiller_vae.py:478-482 = ContextEncoder :92-123, DataEncoder (posterior)
  *                              :126-249, DataDecoder in mode 'train' / 'recon' / 'infer' :345-433; one-shot inference :659-666
@@ -327,6 +337,16 @@ typedef struct glamr_scene_batch {
    * glamr_smpl_backward when the body pose itself depends on optimisation variables (latent-optimisation mode, global_recon_model.py:434-437).
    * Only the reprojection term reaches the joints; rows of joints without weight and of invisible frames are zero. */
   float* g_j_local;                      /* (slots, max_len, n_joints, 3) or NULL */
+  /* out, optional: gradient of the (weighted, normalised) loss of the LAST evaluation w.r.t. traj_local_pred, rows [0, exist_len) indexed like
+   * traj_local_pred; rows beyond and empty slots are zero.  The hand-over to glamr_nets_traj_backward when the trajectory prior stays ATTACHED
+   * (flag_attach_traj_pred: the reference minus the .detach() of global_recon_model.py:396).  Columns 0-8 (dx dy z rot6d): the gradient w.r.t. the
+   * assembled local row = prior + delta, i.e. the data-term part of the gradients of local_xy / local_dxy / local_z / local_rot WITHOUT the
+   * local_traj_*_reg regularisers (they act on the deltas only).  Columns 9-10: the heading angle's gradient (the own element of the reversed
+   * running sum), NOT multiplied by dheading_mask (the mask multiplies the delta, not the prior heading), through
+   * vec_to_heading = torch_safe_atan2(v[10], v[9]) at the prior row.  The full gradient whatever var_mask the stage carries (needs niters >= 1).
+   * Requires grads_out; not with GLAMR_FLAG_ABSOLUTE_HEADING.  Launches with it run on instances of their own: every other launch runs the
+   * code it ran before. */
+  float* g_traj_local;                   /* (slots, max_len, 11) or NULL */
   /* out, optional: the unweighted value of every loss term at EVERY iteration of the launch -- what the reference hands to write_logs after
    * each optimizer.step (global_recon_model.py:564, 646-659: one log line per iteration).  Row it of a scene = the terms evaluated at the
    * parameters iteration it started from (the closure's forward pass), in the order of the GLAMR_LOSS_* ids, like `losses`.  A launch that

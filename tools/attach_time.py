@@ -1,0 +1,59 @@
+"""DEVELOPMENT AID (GPU): latent-optimisation mode with and without the attached trajectory prior (flag_attach_traj_pred), ms per replayed
+iteration for one 300-frame sequence of glamr_dynamic with both latent flags set (slope between a 12- and a 52-iteration run, as
+tools/latent_time.py), and the time of the calls the flag adds (taped predictor instead of the plain one, its backward, the FK backward).
+usage: python tools/attach_time.py"""
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+import bench
+from glamr_amd.global_recon.configs import get_config
+from glamr_amd.global_recon.models import model_dict
+from glamr_amd.utils import synth
+dev = torch.device('cuda:0')
+model = bench.build_model(bench.ensure_assets(), dev)
+md = synth.make_smpl_model()
+one = synth.make_in_dict(seed=0, num_frames=bench.NUM_FRAMES, num_persons=1, smpl_model=md)
+K1, K2 = 12, 52
+
+
+def per_iteration(attach):
+    cfg = get_config(bench.CFG_ID)
+    cfg['grecon_model_specs'].update(flag_opt_motion_latent=True, flag_opt_traj_latent=True, flag_attach_traj_pred=attach)
+    ml = model_dict['global_recon_model'](cfg, dev, None, smpl=model.smpl, mt_model=model.mt_model)
+    ml.optimize(one, max_iters=3)
+
+    def run_k(k):
+        torch.cuda.synchronize()
+        t0 = time.time()
+        ml.optimize(one, max_iters=k)
+        torch.cuda.synchronize()
+        return time.time() - t0
+    t1, t2 = min(run_k(K1), run_k(K1)), min(run_k(K2), run_k(K2))
+    return (t2 - t1) * 1e3 / (K2 - K1)
+
+
+def call_ms(fn, n=20):
+    fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(n):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / n
+
+
+off, on = per_iteration(False), per_iteration(True)
+h = model.mt_model.handle
+T = bench.NUM_FRAMES
+g = torch.Generator(device='cpu').manual_seed(0)
+pose = (torch.randn(1, T, 69, generator=g) * 0.3).to(dev)
+eps = torch.randn(1, 128, generator=g).to(dev)
+G = torch.randn(1, T, 11, generator=g).to(dev)
+_, tape = h.traj_taped([T], eps, in_body_pose=pose)
+gj = h.traj_backward(tape, G)[1]
+print('latent mode, one %d-frame sequence: %.2f ms per iteration detached, %.2f ms attached (+%.2f ms)' % (T, off, on, on - off))
+print('added calls: predictor plain %.3f ms -> taped %.3f ms; traj_backward %.3f ms; fk_backward %.3f ms'
+      % (call_ms(lambda: h.infer(pose, None, [T], traj_eps=eps, infill=False)), call_ms(lambda: h.traj_taped([T], eps, in_body_pose=pose)),
+         call_ms(lambda: h.traj_backward(tape, G)), call_ms(lambda: h.fk_backward(pose, [T], gj))))
