@@ -8,7 +8,8 @@ _LIB = None
 LIB_PATH = os.environ.get('GLAMR_LIB_PATH') or os.path.join(os.path.dirname(os.path.abspath(__file__)), 'libglamr_hip.so')      # (override: A/B runs of kernel variants, tools/README.md)
 NUM_LOSSES = 13
 LOSS_CAMERA_ONLY = (9, 13)    # [first, last) of the camera-only terms: CAM_INV_TRANS_RES_REG, CAM_INV_ROT_SMOOTHNESS, CAM_ORIGIN_SMOOTHNESS, CAM_UP_REG
-LOSS_KP_2D_DIST = 1          # index of the monitor-only keypoint distance in the loss record (GLAMR_LOSS_KP_2D_DIST, include/glamr_hip.h)
+LATENT_REG_ABSENT, LATENT_REG_MONITOR, LATENT_REG_ACTIVE = 0, 1, 2      # GLAMR_LATENT_REG_* (glamr_latent_reg's mode per term)
+LOSS_KP_2D_DIST = 1         # index of the monitor-only keypoint distance in the loss record (GLAMR_LOSS_KP_2D_DIST, include/glamr_hip.h)
 
 
 class TensorDesc(Structure):
@@ -104,6 +105,7 @@ _SIGNATURES = {
     'glamr_adam_coef_table': (c_int, [c_double, c_int, c_void_p]),
     'glamr_adam_step_indexed': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'glamr_counter_add': (c_int, [c_void_p, c_int, c_void_p]),
+    'glamr_latent_reg': (c_int, [c_int, c_int, c_int] + [c_void_p] * 4 + [c_float, c_float] + [c_int] * 4 + [c_void_p] * 4 + [c_int, c_void_p, c_void_p]),
     'glamr_eval_regress_joints': (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'glamr_eval_procrustes': (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'glamr_eval_heading_align': (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

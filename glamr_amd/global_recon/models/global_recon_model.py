@@ -257,6 +257,11 @@ class GlobalReconOptimizer:
         self.flag_attach_traj_pred = bool(g('flag_attach_traj_pred', False))
         if self.flag_attach_traj_pred and not (self.flag_opt_motion_latent or self.flag_opt_traj_latent):
             raise ValueError('flag_attach_traj_pred needs the latent-optimisation mode (flag_opt_motion_latent and / or flag_opt_traj_latent)')
+        # motion_latent_reg / traj_latent_reg (loss_func.py:293-310): run_latent_schedule takes them (glamr_latent_reg), the stage
+        # kernel never sees them.  A term whose latent is not a parameter is refused here.  latent_loss_history[stage]: (scenes, iterations, 2)
+        # UNWEIGHTED values, motion_latent_reg then traj_latent_reg, at the latents each iteration started from (a term the stage does not list: 0).
+        packing.check_latent_regs(self.opt_stage_specs, self.specs)
+        self.latent_loss_history = {}
         self.flag_filter_pose = g('flag_filter_pose', True)
         # keypoint-count filter inside filter_pose (:50-52,264-268); with HybrIK's binary scores (14 scored joints per detected frame) it is all or
         # nothing: the reference's default minimum of 15 removes every frame, 14 or less none
@@ -979,6 +984,8 @@ class GlobalReconOptimizer:
 
     def _forward_only_desc(self, poses_only=False):
         first = next(iter(self.opt_stage_specs.values()))
+        if self.latent_mode:      # (the latent regularisers are run_latent_schedule's, never the stage kernel's; the 'init' forward evaluates no loss)
+            first = dict(first, loss_cfg=packing.split_latent_regs(first['loss_cfg'])[0])
         sd = packing.stage_desc(first, self.specs, has_world_dheading=False, niters=0)
         sd.var_mask = 0
         sd.flags &= ~packing.FLAG_CAM_FROM_PERSON           # stage 'init' keeps the initial camera (:473)
@@ -1226,11 +1233,24 @@ class GlobalReconOptimizer:
         extra = {}
         m, v = torch.zeros_like(params), torch.zeros_like(params)
         step_idx = torch.zeros(3, dtype=torch.int32, device=dev)         # [0] scene parameters, [1] motion latents, [2] trajectory latents: 0-based row of the coefficient table
+        # the latent regularisers (glamr_latent_reg): per-slot window counts (0 = an empty slot) on the host for the argument checks
+        # and on the device for the kernel, the gradient arrays of a latent that has no data gradient in an iteration, the values of the last launch
+        n_win_host = np.ascontiguousarray([num_windows(int(lens[k])) if occupied[k] else 0 for k in range(n_slots)], dtype=np.int32)
+        n_win_dev = torch.as_tensor(n_win_host, device=dev)
+        g_reg_m, g_reg_t = torch.zeros_like(meps), torch.zeros_like(teps)
+        reg_values = torch.zeros((S, 2), device=dev)
+        self.latent_loss_history = {}
         has_wd = False
         use_graph = os.environ.get('GLAMR_LATENT_GRAPH', '1') != '0'
         self.latent_graph_replays = 0
 
-        def iteration(spec, with_priors, first, coef):
+        def adam_latent(x, m_x, v_x, g, coef, idx):
+            # (a parameter's step count advances only when it has a gradient: the latents have their own indices)
+            _lib.check(L.glamr_adam_step_indexed(x.numel(), _lib.ptr(x), _lib.ptr(m_x), _lib.ptr(v_x), _lib.ptr(g), _lib.ptr(coef), _lib.ptr(step_idx[idx:]),
+                                                 _lib.current_stream()))
+            _lib.check(L.glamr_counter_add(_lib.ptr(step_idx[idx:]), 1, _lib.current_stream()))
+
+        def iteration(spec, with_priors, first, coef, regs=None, hist=None):
             """One Adam iteration (:547-570 in latent mode), launches only -- nothing here reads a value back or depends on the iteration
             number except through `step_idx` on the device, so the same launch sequence is captured ONCE per stage and replayed."""
             tape = ttape = None
@@ -1265,10 +1285,8 @@ class GlobalReconOptimizer:
                 extra['g_traj_latent'] = g_tl
                 if g_joints is not None:
                     g_bp = h.fk_backward(pose_out, lens_t, g_joints)
-                if self.flag_opt_traj_latent:
-                    _lib.check(L.glamr_adam_step_indexed(teps.numel(), _lib.ptr(teps), _lib.ptr(m_tl), _lib.ptr(v_tl), _lib.ptr(g_tl), _lib.ptr(coef), _lib.ptr(step_idx[2:]),
-                                                         _lib.current_stream()))
-                    _lib.check(L.glamr_counter_add(_lib.ptr(step_idx[2:]), 1, _lib.current_stream()))
+                if self.flag_opt_traj_latent and regs is None:
+                    adam_latent(teps, m_tl, v_tl, g_tl, coef, 2)
             if tape is not None and self.flag_opt_motion_latent:
                 # dL/d j_local -> body pose (skinning, blend shapes, chain, re-anchoring in reverse) -> latents (all windows)
                 pose72 = torch.cat([zeros3, pa['smpl_pose'].view(-1, 69)], dim=1).contiguous()
@@ -1281,10 +1299,30 @@ class GlobalReconOptimizer:
                 if g_bp is not None:
                     g_out += g_bp.view(-1, 69)
                 g_lat = h.infill_backward(tape, g_out.view(n_slots, T, 69))
-                # (a parameter's step count advances only when it has a gradient: the latents have their own index)
-                _lib.check(L.glamr_adam_step_indexed(meps.numel(), _lib.ptr(meps), _lib.ptr(m_lat), _lib.ptr(v_lat), _lib.ptr(g_lat), _lib.ptr(coef), _lib.ptr(step_idx[1:]),
-                                                     _lib.current_stream()))
-                _lib.check(L.glamr_counter_add(_lib.ptr(step_idx[1:]), 1, _lib.current_stream()))
+                if regs is None:
+                    adam_latent(meps, m_lat, v_lat, g_lat, coef, 1)
+            if regs is not None:
+                # A stage with a latent regulariser (compute_loss :533-545 evaluates it in EVERY iteration, also before opt_latent_start_iter): one
+                # launch for both latents, at the latents this iteration started from.  A latent that has a data gradient gets the regulariser's
+                # ADDED to it, one that has none gets it STORED -- and is stepped by it alone (traj_latent in detached mode; both latents before
+                # opt_latent_start_iter, when the priors are not re-run).  One Adam step per latent that has any gradient.
+                (w_m, mode_m), (w_t, mode_t) = regs
+                g_t_data = extra.get('g_traj_latent') if (ttape is not None and self.flag_opt_traj_latent) else None
+                g_m = g_lat if g_lat is not None else g_reg_m
+                g_t = g_t_data if g_t_data is not None else g_reg_t
+                _lib.check(L.glamr_latent_reg(S, P, meps.shape[1], _lib.ptr(meps), _lib.ptr(teps), _lib.ptr(n_win_dev), _lib.ptr(n_win_host), w_m, w_t, mode_m, mode_t,
+                                              int(g_lat is not None), int(g_t_data is not None), _lib.ptr(g_m), _lib.ptr(g_t), _lib.ptr(reg_values),
+                                              _lib.ptr(hist), 0 if hist is None else hist.shape[1], _lib.ptr(step_idx), _lib.current_stream()))
+                if g_t_data is not None or mode_t == _lib.LATENT_REG_ACTIVE:
+                    extra['g_traj_latent_total'] = g_t
+                    adam_latent(teps, m_tl, v_tl, g_t, coef, 2)
+                else:
+                    extra.pop('g_traj_latent_total', None)
+                if g_lat is not None or mode_m == _lib.LATENT_REG_ACTIVE:
+                    extra['g_motion_latent_total'] = g_m
+                    adam_latent(meps, m_lat, v_lat, g_m, coef, 1)
+                else:
+                    extra.pop('g_motion_latent_total', None)
             _lib.check(L.glamr_adam_step_indexed(params.numel(), _lib.ptr(params), _lib.ptr(m), _lib.ptr(v), _lib.ptr(grads), _lib.ptr(coef), _lib.ptr(step_idx),
                                                  _lib.current_stream()))
             _lib.check(L.glamr_counter_add(_lib.ptr(step_idx), 1, _lib.current_stream()))
@@ -1298,6 +1336,14 @@ class GlobalReconOptimizer:
             tab = np.empty(2 * max(n, 1), np.float32)
             _lib.check(L.glamr_adam_coef_table(float(spec['opt_lr']), max(n, 1), tab.ctypes.data_as(ctypes.c_void_p)))
             coef = torch.as_tensor(tab, device=dev)
+            # the latent regularisers are this loop's, not the stage kernel's: the launch gets the loss_cfg without them
+            rest_cfg, regs = packing.split_latent_regs(spec['loss_cfg'])
+            hist = None
+            if any(mode != _lib.LATENT_REG_ABSENT for _, mode in regs):
+                spec = dict(spec, loss_cfg=rest_cfg)
+                hist = torch.zeros((S, max(n, 1), 2), device=dev)
+            else:
+                regs = None                                              # (no regulariser: today's launch sequence, launch for launch)
             graph = None
             for it in range(n):
                 with_priors = it >= start
@@ -1305,8 +1351,11 @@ class GlobalReconOptimizer:
                     graph.replay()
                     self.latent_graph_replays += 1
                     continue
-                g_lat = iteration(spec, with_priors, it == 0, coef)
-                if (g_lat is not None or (with_priors and attach)) and getattr(self, 'latent_trace', None) is not None and not self.latent_trace:      # first gradient of the run, for the parity tests
+                g_lat = iteration(spec, with_priors, it == 0, coef, regs, hist)
+                trace = getattr(self, 'latent_trace', None)
+                if regs is not None and trace is not None and 'latent_reg' not in trace:      # the two values of the run's first regularised iteration
+                    trace['latent_reg'] = reg_values.detach().cpu().numpy()
+                if (g_lat is not None or (with_priors and (attach or regs is not None))) and trace is not None and 'losses' not in trace:      # first gradient of the run, for the parity tests
                     self.latent_trace.update(losses=packed.t['losses'].detach().cpu().numpy(),
                                              smpl_pose=pa['smpl_pose'].detach().cpu().numpy(), traj_local_pred=packed.t['traj_local_pred'].detach().cpu().numpy())
                     if g_lat is not None:
@@ -1314,6 +1363,8 @@ class GlobalReconOptimizer:
                     if attach:
                         self.latent_trace.update(g_traj_latent=extra['g_traj_latent'].detach().cpu().numpy(),
                                                  g_traj_local=g_traj_local.detach().cpu().numpy())
+                    elif 'g_traj_latent_total' in extra:                  # detached mode: the regulariser is traj_latent's whole gradient
+                        self.latent_trace['g_traj_latent'] = extra['g_traj_latent_total'].detach().cpu().numpy()
                 # from here on every iteration of the stage is the same launch sequence: capture it once, replay it n - it - 2 times
                 if use_graph and with_priors and it >= 1 and n - it - 1 >= 2 and not torch.cuda.is_current_stream_capturing():
                     try:
@@ -1322,7 +1373,7 @@ class GlobalReconOptimizer:
                         side = self.__dict__.setdefault('_latent_capture_stream', torch.cuda.Stream(device=dev))
                         side.wait_stream(cur)
                         with torch.cuda.graph(g, stream=side):
-                            iteration(spec, True, False, coef)
+                            iteration(spec, True, False, coef, regs, hist)
                         cur.wait_stream(side)
                         graph = g
                     except Exception as e:      # noqa: BLE001 -- the plain launches are always available
@@ -1334,12 +1385,28 @@ class GlobalReconOptimizer:
             if spec.get('reinitialize_cam', False):
                 packed.t['cam_pose'][:] = packed.t['cam_pose'][:, :1]
             del graph
+            if hist is not None:
+                self._report_latent_stage(packed, stage, spec, regs, hist[:, :n])
         packed.has_world_dheading = has_wd
         packed.stage_ws = []
         packed.latents = (meps, teps)
         packed.t['g_j_local'] = None
         packed.t['g_traj_local'] = None
         return packed
+
+    def _report_latent_stage(self, packed, stage, spec, regs, hist):
+        """latent_loss_history[stage] and, with a `log`, write_logs' line (:646-659) per iteration for the stage's latent regularisers under the
+        reference's names (the unweighted values, loss_uw_dict :564).  The latent-optimisation schedule records no other term per iteration."""
+        h = hist.cpu().numpy()                                          # (waits for the stage)
+        self.latent_loss_history[stage] = h
+        if self.log is None:
+            return
+        names = [(t, n) for t, n in enumerate(packing.LATENT_REG_TERMS) if regs[t][1] != _lib.LATENT_REG_ABSENT]
+        seqs = getattr(packed, 'seq_names', None) or ['seq%d' % si for si in range(packed.S)]
+        for si in range(packed.S):
+            for it in range(h.shape[1]):
+                loss_str = ' | '.join('%s: %7.3f' % (n, h[si, it, t]) for t, n in names)
+                self.log.info('%s - %s - %s | %4d/%d | LR: %.0e | %s' % (self.cfg_id, seqs[si], stage, it, h.shape[1], spec['opt_lr'], loss_str))
 
     def collect(self, datas, packed, fetched=None):
         """Device arrays -> the reference's output dictionaries (numpy): one device->host copy per array.  Waits for this batch only."""

@@ -21,6 +21,30 @@ FLAG_KEEP_TABLES = 256                                     # launch-by-launch sc
 FLAG_NO_REPORT = 128                                       # launch-by-launch schedules: the launch's last evaluation writes no outputs / loss values
 FLAG_ABSOLUTE_HEADING = 64                                 # specs absolute_heading: per-frame headings are absolute (csrc/grecon_wide.hip instances)
 
+# The latent regularisers (loss_func.py:293-310), in the order of glamr_latent_reg's terms, with the flag that makes each one's
+# latent an Adam parameter.  They are NOT terms of the fused stage kernel (stage_desc refuses them): run_latent_schedule takes them itself.
+LATENT_REG_TERMS = {'motion_latent_reg': 'flag_opt_motion_latent', 'traj_latent_reg': 'flag_opt_traj_latent'}
+
+
+def split_latent_regs(loss_cfg):
+    """loss_cfg -> (loss_cfg without the latent regularisers, [(weight, GLAMR_LATENT_REG_* mode)] for motion_latent_reg, traj_latent_reg)."""
+    rest = {n: c for n, c in loss_cfg.items() if n not in LATENT_REG_TERMS}
+    regs = []
+    for name in LATENT_REG_TERMS:
+        c = loss_cfg.get(name)
+        mode = _lib.LATENT_REG_ABSENT if c is None else _lib.LATENT_REG_MONITOR if c.get('monitor_only', False) else _lib.LATENT_REG_ACTIVE
+        regs.append((0.0 if c is None else float(c['weight']), mode))
+    return rest, regs
+
+
+def check_latent_regs(opt_stage_specs, model_specs):
+    """A latent regulariser reads `motion_latent` / `traj_latent` of pose_dict, which exist only when the latent is a parameter
+    (global_recon_model.py:155-158): a KeyError in the reference, a ValueError here, before anything runs."""
+    for stage, spec in opt_stage_specs.items():
+        for name, flag in LATENT_REG_TERMS.items():
+            if name in spec['loss_cfg'] and not model_specs.get(flag, False):
+                raise ValueError('loss %r in stage %r needs %s in grecon_model_specs: the term regularises a latent that is not a parameter' % (name, stage, flag))
+
 
 def param_layout_py(max_persons, max_len):
     """Mirror of glamr::grecon::param_layout (glamr_amd/csrc/grecon_algo.hpp); checked against the library in the tests."""

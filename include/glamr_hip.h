@@ -395,6 +395,30 @@ int glamr_adam_step_indexed(int n, float* params, float* exp_avg, float* exp_avg
                             const int32_t* step_index, void* stream);
 int glamr_counter_add(int32_t* counter, int value, void* stream);
 
+/* The latent regularisers of the latent-optimisation mode (csrc/latent_reg.hip) -- replaces motion_latent_reg_loss and
+ * traj_latent_reg_loss (global_recon/models/loss_func.py:293-310), their weighting in compute_loss (global_recon_model.py:533-545) and their
+ * part of `loss.backward()` (:556).  One launch serves both latents of a batch, one workgroup per scene (scene s = slots
+ * [s * max_persons, (s + 1) * max_persons), as in glamr_scene_batch).  Term 0 is motion_latent_reg, term 1 traj_latent_reg:
+ *   value[0] = sum over the scene's persons of sum(motion_latent^2) / (the scene's number of infiller windows),
+ *   value[1] = sum over the scene's persons of sum(traj_latent^2)   / (the scene's number of persons).
+ * meps dev (slots, n_win_max, 128): slot k holds n_win_slot[k] real rows; teps dev (slots, 128): slot k is real iff n_win_slot[k] > 0 (0 = an
+ * empty slot).  Padded rows and empty slots are never read, enter no sum and no count.  n_win_slot is read by the kernel (dev int32, so a
+ * captured launch carries no host pointer); n_win_slot_host is the HOST copy of the same table, which the argument checks read:
+ * 0 <= n_win_slot[k] <= n_win_max, and a scene has at least one person when a term is ACTIVE.
+ * mode_*: GLAMR_LATENT_REG_ABSENT (nothing of the term is read or written), _MONITOR (monitor_only: the value and no gradient) or _ACTIVE.
+ * An ACTIVE term writes g = fl(fl(weight / rows) * 2 z) (fp32, rows = the denominator above) to its gradient array g_meps / g_teps (dev, the
+ * latent's shape): add_* != 0 ADDS it to what the array holds (the latent also has a data gradient this iteration; padded rows are left
+ * alone), add_* == 0 STORES it (padded rows and empty slots are stored as zero).  values dev (n_scenes, 2): the UNWEIGHTED values; history
+ * (may be NULL) dev (n_scenes, n_rows, 2): row *row_index (dev int32, 0 <= *row_index < n_rows, otherwise no row is written) receives the
+ * same values -- a replayed graph writes the right row because the caller advances the index on the stream (glamr_counter_add).
+ * meps, teps, g_meps, g_teps 16-byte aligned.  Fixed summation order, no atomics: a repeat on the same inputs is bit-equal. */
+#define GLAMR_LATENT_REG_ABSENT 0
+#define GLAMR_LATENT_REG_MONITOR 1
+#define GLAMR_LATENT_REG_ACTIVE 2
+int glamr_latent_reg(int n_scenes, int max_persons, int n_win_max, const float* meps, const float* teps, const int32_t* n_win_slot,
+                     const int32_t* n_win_slot_host, float weight_motion, float weight_traj, int mode_motion, int mode_traj, int add_motion,
+                     int add_traj, float* g_meps, float* g_teps, float* values, float* history, int n_rows, const int32_t* row_index, void* stream);
+
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * Device-side init_data -- replaces GlobalReconOptimizer.init_data (global_recon_model.py:76-248) between the HybrIK wire format

@@ -1,7 +1,9 @@
 """DEVELOPMENT AID (GPU): latent-optimisation mode with and without the attached trajectory prior (flag_attach_traj_pred), ms per replayed
 iteration for one 300-frame sequence of glamr_dynamic with both latent flags set (slope between a 12- and a 52-iteration run, as
 tools/latent_time.py), and the time of the calls the flag adds (taped predictor instead of the plain one, its backward, the FK backward).
-usage: python tools/attach_time.py"""
+--reg: the same two figures with the latent regularisers (motion_latent_reg / traj_latent_reg) in the stage, and the time of
+one glamr_latent_reg launch alone.
+usage: python tools/attach_time.py [--reg]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -16,8 +18,14 @@ one = synth.make_in_dict(seed=0, num_frames=bench.NUM_FRAMES, num_persons=1, smp
 K1, K2 = 12, 52
 
 
+REG = '--reg' in sys.argv
+
+
 def per_iteration(attach):
     cfg = get_config(bench.CFG_ID)
+    if REG:
+        for spec in cfg['opt_stage_specs'].values():
+            spec['loss_cfg'].update(motion_latent_reg=dict(weight=20.0), traj_latent_reg=dict(weight=3000.0))
     cfg['grecon_model_specs'].update(flag_opt_motion_latent=True, flag_opt_traj_latent=True, flag_attach_traj_pred=attach)
     ml = model_dict['global_recon_model'](cfg, dev, None, smpl=model.smpl, mt_model=model.mt_model)
     ml.optimize(one, max_iters=3)
@@ -57,3 +65,14 @@ print('latent mode, one %d-frame sequence: %.2f ms per iteration detached, %.2f 
 print('added calls: predictor plain %.3f ms -> taped %.3f ms; traj_backward %.3f ms; fk_backward %.3f ms'
       % (call_ms(lambda: h.infer(pose, None, [T], traj_eps=eps, infill=False)), call_ms(lambda: h.traj_taped([T], eps, in_body_pose=pose)),
          call_ms(lambda: h.traj_backward(tape, G)), call_ms(lambda: h.fk_backward(pose, [T], gj))))
+if REG:
+    import numpy as np
+    from glamr_amd import _lib
+    from glamr_amd.models.priors import num_windows
+    nw = np.array([num_windows(T)], np.int32)
+    nw_dev, meps = torch.as_tensor(nw, device=dev), torch.randn(1, int(nw[0]), 128, generator=g).to(dev)
+    g_m, g_t, vals = torch.zeros_like(meps), torch.zeros_like(eps), torch.zeros(1, 2, device=dev)
+    L = _lib.lib()
+    print('with the latent regularisers in the stage (figures above); glamr_latent_reg alone: %.4f ms'
+          % call_ms(lambda: _lib.check(L.glamr_latent_reg(1, 1, int(nw[0]), _lib.ptr(meps), _lib.ptr(eps), _lib.ptr(nw_dev), _lib.ptr(nw), 20.0, 3000.0, 2, 2, 0, 0, _lib.ptr(g_m),
+                                                          _lib.ptr(g_t), _lib.ptr(vals), None, 0, None, _lib.current_stream())), n=200))
