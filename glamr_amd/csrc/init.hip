@@ -233,10 +233,16 @@ __device__ void person_transform(const float aa[3], const float tr[3], float M[1
   rm::aa_to_rotmat_k(aa, R);
   for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) M[i * 4 + j] = R[i * 3 + j]; M[i * 4 + 3] = tr[i]; }
 }
+// Three products summed from +0, as the reference's matmul and sum() accumulate: the same number for every other operand, but +0 instead of -0
+// where all three products are -0 -- the zero matrices of init_cam_pose carry signed zeros, and their signs are part of the contract
+// (cam_all_frames_kernel below)
+__device__ __forceinline__ float dot3_from_zero(float a0, float b0, float a1, float b1, float a2, float b2) {
+  return 0.f + a0 * b0 + a1 * b1 + a2 * b2;
+}
 __device__ void inv34(const float M[12], float O[12]) {
   for (int i = 0; i < 3; ++i) {
     for (int j = 0; j < 3; ++j) O[i * 4 + j] = M[j * 4 + i];
-    O[i * 4 + 3] = -(M[3] * M[i] + M[7] * M[4 + i] + M[11] * M[8 + i]);
+    O[i * 4 + 3] = -dot3_from_zero(M[3], M[i], M[7], M[4 + i], M[11], M[8 + i]);
   }
 }
 __device__ void mul34(const float A[12], const float B[12], float C[12]) {
@@ -248,9 +254,13 @@ __device__ void mul34(const float A[12], const float B[12], float C[12]) {
 // re-orthonormalise the rotation block through the 6D representation (rot6d_to_rotmat(rotmat_to_rot6d(.)) :315)
 __device__ void reortho(float M[12]) {
   const float d6[6] = {M[0], M[4], M[8], M[1], M[5], M[9]};
-  float R[9];
-  rm::rot6d_to_rotmat(d6, R);
-  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) M[i * 4 + j] = R[i * 3 + j];
+  float b1[3], b2[3], b3[3], u[3];      // rm::rot6d_to_rotmat with the projection summed from +0 (torch's sum(-1))
+  rm::normalize3(d6, b1);
+  const float dot = dot3_from_zero(b1[0], d6[3], b1[1], d6[4], b1[2], d6[5]);
+  for (int i = 0; i < 3; ++i) u[i] = d6[3 + i] - dot * b1[i];
+  rm::normalize3(u, b2);
+  rm::cross3(b1, b2, b3);
+  for (int i = 0; i < 3; ++i) { M[i * 4 + 0] = b1[i]; M[i * 4 + 1] = b2[i]; M[i * 4 + 2] = b3[i]; }
 }
 // quaternion_to_rotation_matrix (kornia: normalises first)
 __device__ void quat_to_rotmat(const float q_[4], float R[9]) {
