@@ -89,6 +89,8 @@ _SIGNATURES = {
     'glamr_nets_traj_clip': (c_int, [c_void_p, c_int, c_int, c_int, POINTER(TrajIO), c_void_p, c_void_p]),
     'glamr_traj_local_to_global_workspace_bytes': (c_size_t, [c_int, c_int]),
     'glamr_traj_local_to_global': (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'glamr_traj_local_to_global_backward_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'glamr_traj_local_to_global_backward': (c_int, [c_int, c_int] + [c_void_p] * 8),
     'glamr_host_scatter': (c_int, [c_int, c_void_p, c_int, POINTER(HostStaging), c_void_p, c_void_p, c_int]),
     'glamr_init_workspace_bytes': (c_size_t, [c_int, c_int]),
     'glamr_init_prepare': (c_int, [POINTER(RawBatch), POINTER(SceneBatch), POINTER(PersonArrays), POINTER(FilterOpts), c_void_p, c_void_p]),

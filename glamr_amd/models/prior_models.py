@@ -18,9 +18,10 @@ import numpy as np
 import torch
 
 from .layouts import INFILLER_LAYOUT, TRAJPRED_LAYOUT
-from .priors import MotionPriorsHandle, num_windows, local_to_global, NZ, PAST, CUR, VAE_INFER, VAE_TRAIN, VAE_RECON
+from .priors import MotionPriorsHandle, num_windows, local_to_global, local_to_global_backward, NZ, PAST, CUR, VAE_INFER, VAE_TRAIN, VAE_RECON
 from ..lib.utils.dist import Normal
 from . import latent_rng
+from .. import _lib
 
 FUT = 10
 SMPL_PARENTS = [-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19, 20, 21]
@@ -94,6 +95,27 @@ class _PriorBase:
         return self.forward(data)
 
 
+def _lens_list(lens, B, T):
+    lens = [T] * B if lens is None else [int(n) for n in lens]
+    if len(lens) != B or any(n < 1 or n > T for n in lens):
+        raise ValueError('lens must hold one length in [1, %d] per sequence (%d sequences), got %s' % (T, B, lens))
+    return lens
+
+
+class _Infill(torch.autograd.Function):
+    """MotionInfillerVAE.infill: the forward is glamr_nets_infill_taped, the backward glamr_nets_infill_backward (no arithmetic on the host)."""
+
+    @staticmethod
+    def forward(ctx, in_motion_latent, handle, in_body_pose, visible, lens):
+        out, tape = handle.infill_taped(in_body_pose, visible, lens, in_motion_latent.detach())
+        ctx.handle, ctx.tape = handle, tape
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.handle.infill_backward(ctx.tape, g), None, None, None, None
+
+
 class MotionInfillerVAE(_PriorBase):
     LAYOUT = INFILLER_LAYOUT
     model_type = 'angle'
@@ -106,6 +128,24 @@ class MotionInfillerVAE(_PriorBase):
         if self._handle is None:
             self._handle = MotionPriorsHandle(self._sd, _zeros_sd(TRAJPRED_LAYOUT), np.zeros((24, 3), np.float32), SMPL_PARENTS, self.device)
         return self._handle
+
+    def infill(self, in_body_pose, frame_mask, in_motion_latent, lens=None):
+        """The infilled body pose (B,T,69) of the sliding-window inference (multi_step=True, one sample) as a DIFFERENTIABLE function of the latent
+        draws in_motion_latent (B, windows, 128): glamr_nets_infill_taped forward, glamr_nets_infill_backward backward.  in_body_pose (B,T,69),
+        frame_mask (B,T) 1 = visible, lens: frames per sequence (default: all T).  The gradient reaches in_motion_latent ONLY: the VJP with
+        respect to in_body_pose does not exist, and an in_body_pose that requires grad is refused rather than handed a gradient of None."""
+        if torch.is_tensor(in_body_pose) and in_body_pose.requires_grad:
+            raise NotImplementedError('MotionInfillerVAE.infill has no gradient with respect to in_body_pose (only in_motion_latent is differentiated); detach it')
+        h = self._ensure_handle()
+        pose = in_body_pose.to(self.device).float()
+        if pose.dim() != 3 or pose.shape[-1] != 69:
+            raise ValueError('in_body_pose must be (B, T, 69), got %s' % (tuple(pose.shape),))
+        B, T = pose.shape[:2]
+        eps = in_motion_latent.to(self.device)
+        if eps.dim() != 3 or eps.shape[0] != B or eps.shape[1] < num_windows(T) or eps.shape[2] != NZ:
+            raise ValueError('in_motion_latent must be (%d, >= %d, %d), got %s' % (B, num_windows(T), NZ, tuple(eps.shape)))
+        vis = (frame_mask.to(self.device) == 1).float()
+        return _Infill.apply(eps.float(), h, pose, vis, _lens_list(lens, B, T))
 
     def init_batch_data(self, batch):
         """motion_infiller_vae.py:495-549 (use_joints False, axis-angle, no pose dropout at inference): layout only."""
@@ -284,6 +324,46 @@ class _LocalTraj(torch.autograd.Function):
         return g_joints, g_eps, None, None
 
 
+class _LocalTrajPose(torch.autograd.Function):
+    """TrajPredVAE.local_traj(in_body_pose=...): the forward is glamr_nets_traj_taped with the FK kernel inside (as glamr_nets_infer runs it), the
+    backward glamr_nets_traj_backward followed by glamr_nets_fk_backward (no arithmetic on the host)."""
+
+    @staticmethod
+    def forward(ctx, in_body_pose, in_traj_latent, handle, lens):
+        pose = in_body_pose.detach().float().contiguous()
+        out, tape = handle.traj_taped(lens, in_traj_latent.detach(), in_body_pose=pose)
+        ctx.handle, ctx.tape, ctx.lens = handle, tape, lens
+        ctx.save_for_backward(pose)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (pose,) = ctx.saved_tensors
+        g_eps, g_joints = ctx.handle.traj_backward(ctx.tape, g, want_joints=ctx.needs_input_grad[0])
+        g_pose = ctx.handle.fk_backward(pose, ctx.lens, g_joints) if ctx.needs_input_grad[0] else None
+        return g_pose, g_eps, None, None
+
+
+class _GlobalTraj(torch.autograd.Function):
+    """TrajPredVAE.global_traj: the forward is glamr_traj_local_to_global, the backward glamr_traj_local_to_global_backward (no arithmetic on
+    the host).  Outputs nobody differentiates arrive as None and go to the library as NULL."""
+
+    @staticmethod
+    def forward(ctx, local_traj, lens_dev):
+        local = local_traj.detach().float().contiguous()
+        ctx.lens_dev = lens_dev
+        ctx.save_for_backward(local)
+        ctx.set_materialize_grads(False)
+        return local_to_global(local)
+
+    @staticmethod
+    def backward(ctx, g_trans, g_orient, g_orient_q):
+        (local,) = ctx.saved_tensors
+        if g_trans is None and g_orient is None and g_orient_q is None:
+            return None, None
+        return local_to_global_backward(local, ctx.lens_dev, g_trans, g_orient, g_orient_q), None
+
+
 class _JointPos(torch.autograd.Function):
     """TrajPredVAE.joint_pos: the forward is get_joint_pos, the backward glamr_nets_fk_backward (no arithmetic on the host)."""
 
@@ -321,14 +401,35 @@ class TrajPredVAE(_PriorBase):
 
     seq_len = 100            # chunk length of the multi-step (chunked) inference, traj_pred_demo.yml
 
-    def local_traj(self, in_joint_pos, in_traj_latent, lens=None):
+    def local_traj(self, in_joint_pos, in_traj_latent, lens=None, in_body_pose=None):
         """The predicted local trajectory (B,T,11) of inference mode as a DIFFERENTIABLE function of the joint rows in_joint_pos (B,T,69) and the
         latent draw in_traj_latent (B,128); lens: frames per sequence (default: all T).  The reference detaches this output
-        (global_recon_model.py:396); here gradients reach both inputs through glamr_nets_traj_backward."""
+        (global_recon_model.py:396); here gradients reach both inputs through glamr_nets_traj_backward.
+        in_body_pose (B,T,69) instead of in_joint_pos (pass None for it; giving both is a ValueError): the forward-kinematics kernel runs inside
+        the call, as in glamr_nets_infer -- the rows are the plain inference's bit for bit --, and the gradient reaches the body pose through
+        glamr_nets_fk_backward."""
+        if (in_joint_pos is None) == (in_body_pose is None):
+            raise ValueError('exactly one of in_joint_pos and in_body_pose must be given')
         h = self._ensure_handle()
-        B, T = in_joint_pos.shape[:2]
+        src = in_joint_pos if in_joint_pos is not None else in_body_pose
+        B, T = src.shape[:2]
         lens = [T] * B if lens is None else [int(n) for n in lens]
+        if in_body_pose is not None:
+            return _LocalTrajPose.apply(in_body_pose.to(self.device), in_traj_latent.to(self.device), h, lens)
         return _LocalTraj.apply(in_joint_pos, in_traj_latent, h, lens)
+
+    def global_traj(self, local_traj, lens=None):
+        """traj_local2global_heading + quaternion_to_angle_axis as a DIFFERENTIABLE function of the local rows (B,T,11): returns
+        (trans (B,T,3), orient axis-angle (B,T,3), orient_q (B,T,4)); glamr_traj_local_to_global forward (the values of priors.local_to_global),
+        glamr_traj_local_to_global_backward backward.  lens: frames per sequence (default: all T).  The forward always runs over all T rows:
+        rows at or beyond a sequence's length are forward values that NO gradient flows through -- upstream gradients there are ignored and
+        the gradient of those local rows is zero."""
+        local_traj = local_traj.to(self.device)
+        if local_traj.dim() != 3 or local_traj.shape[-1] != 11:
+            raise ValueError('local_traj must be (B, T, 11), got %s' % (tuple(local_traj.shape),))
+        B, T = local_traj.shape[:2]
+        lens_dev = None if lens is None else torch.tensor(_lens_list(lens, B, T), dtype=torch.int32).to(self.device)
+        return _GlobalTraj.apply(local_traj, lens_dev)
 
     def joint_pos(self, body_pose, lens=None):
         """get_joint_pos as a DIFFERENTIABLE function of body_pose (B,T,69): the joint rows (B,T,69) the predictor reads, so that
@@ -647,6 +748,51 @@ class MotionTrajJointModel:
                 for key in ('recon_out_pose', 'recon_out_trans', 'recon_out_orient', 'recon_out_local_traj_tp'):
                     if key in out:
                         data[key] = out[key]
+
+    def inference_grad(self, batch, lens=None):
+        """The differentiable twin of inference(batch, sample_num=1) for the call GLAMR makes: batch = {'in_body_pose' (B,T,69), 'frame_mask' (B,T)
+        1 = visible, 'in_motion_latent' (B, windows, 128) -- (windows, 128) with B = 1 --, 'in_traj_latent' (B,128) -- (1,128) with B = 1}.  Same
+        keys, shapes and VALUES (bit for bit under the same latents) as inference: infer_out_body_pose (B,1,T,69), infer_out_local_traj_tp
+        (T,B,1,11), infer_out_trans / infer_out_orient (B,1,T,3), infer_out_pose (B,1,T,72) -- but every one carries an autograd graph back to
+        both latents (infill -> local_traj(in_body_pose=...) -> global_traj; the trajectory's gradient reaches in_motion_latent through the
+        forward kinematics and the predictor).  lens: frames per sequence (default, as inference: all T); rows at or beyond a length are
+        forward values without a gradient.  Keeps the two tapes (glamr_nets_tape_bytes + glamr_nets_traj_tape_bytes) until the graph is freed."""
+        for k in ('in_body_pose', 'frame_mask'):
+            if k not in batch:
+                raise ValueError('inference_grad needs batch[%r]' % k)
+        for k in ('in_motion_latent', 'in_traj_latent'):
+            if batch.get(k) is None:
+                raise ValueError('inference_grad differentiates with respect to the latents: batch[%r] is missing' % k)
+        for k in ('pose', 'trans', 'init_xy', 'init_heading'):
+            if k in batch:
+                raise ValueError('inference_grad covers the inference call without ground truth: batch[%r] is not supported' % k)
+        pose = batch['in_body_pose'].to(self.device).float()
+        B, T = pose.shape[:2]
+        nw = num_windows(T)
+        me, te = batch['in_motion_latent'].to(self.device), batch['in_traj_latent'].to(self.device)
+        if me.dim() == 2 and B == 1:
+            me = me.unsqueeze(0)
+        if tuple(me.shape) != (B, nw, NZ):
+            raise ValueError('in_motion_latent must be (%d, %d, %d)%s, got %s' % (B, nw, NZ, ' or (%d, %d)' % (nw, NZ) if B == 1 else '', tuple(batch['in_motion_latent'].shape)))
+        if tuple(te.shape) != (B, NZ):
+            raise ValueError('in_traj_latent must be (%d, %d), got %s' % (B, NZ, tuple(te.shape)))
+        lens = _lens_list(lens, B, T)
+        L = _lib.lib()
+        tape = L.glamr_nets_tape_bytes(self.handle.h, B, T) + L.glamr_nets_traj_tape_bytes(self.handle.h, B, T)
+        free = torch.cuda.mem_get_info(self.device)[0] + torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
+        if tape > free:
+            raise ValueError('inference_grad keeps every activation of the infiller and of the trajectory predictor for its backward: %.1f GB for %d sequences of %d frames, '
+                             '%.1f GB of device memory are free; run it on smaller batches' % (tape / 2.0 ** 30, B, T, free / 2.0 ** 30))
+        body = self.mfiller.infill(pose, batch['frame_mask'], me, lens=lens)
+        local = self.traj_predictor.local_traj(None, te, lens=lens, in_body_pose=body)
+        trans, orient, _ = self.traj_predictor.global_traj(local, lens=lens)
+        data = dict(batch)
+        data['infer_out_body_pose'] = body.unsqueeze(1)
+        data['infer_out_orient'] = orient.unsqueeze(1)
+        data['infer_out_trans'] = trans.unsqueeze(1)
+        data['infer_out_pose'] = torch.cat([data['infer_out_orient'], data['infer_out_body_pose']], dim=-1)
+        data['infer_out_local_traj_tp'] = local.unsqueeze(1).permute(2, 0, 1, 3).contiguous()
+        return data
 
     def inference(self, batch, sample_num=5, recon=False):
         """motion_traj_joint_model.py:141-145"""

@@ -260,3 +260,31 @@ def local_to_global(local_traj):
     ws = torch.empty(L.glamr_traj_local_to_global_workspace_bytes(B, T), dtype=torch.uint8, device=dev)
     _lib.check(L.glamr_traj_local_to_global(B, T, _lib.ptr(local_traj), _lib.ptr(trans), _lib.ptr(orient), _lib.ptr(q), _lib.ptr(ws), _lib.current_stream()))
     return trans, orient, q
+
+
+def local_to_global_backward(local_traj, lens, g_trans=None, g_orient=None, g_orient_q=None):
+    """The vector-Jacobian product of local_to_global (glamr_traj_local_to_global_backward): dL/d local_traj (B,T,11) for upstream gradients of
+    trans (B,T,3), the axis-angle orient (B,T,3) and the quaternion (B,T,4); at least one is given, the given ones add up.  local_traj is what
+    the forward was given.  lens: an int32 DEVICE tensor (B,), a list of ints, or None = T frames everywhere; rows at or beyond a length are
+    not read from the upstream gradients and are zero in the result."""
+    L = _lib.lib()
+    local_traj = local_traj.float().contiguous()
+    B, T = local_traj.shape[:2]
+    dev = local_traj.device
+    if g_trans is None and g_orient is None and g_orient_q is None:
+        raise ValueError('at least one of g_trans, g_orient and g_orient_q must be given')
+    if lens is not None and not torch.is_tensor(lens):
+        lens = torch.tensor([int(n) for n in lens], dtype=torch.int32).to(dev)
+    if lens is not None:
+        lens = lens.to(device=dev, dtype=torch.int32).contiguous()
+        if lens.numel() != B:
+            raise ValueError('lens has %d entries for %d sequences' % (lens.numel(), B))
+    g = [None if t is None else t.to(dev).float().contiguous() for t in (g_trans, g_orient, g_orient_q)]
+    for t, w in zip(g, (3, 3, 4)):
+        if t is not None and tuple(t.shape) != (B, T, w):
+            raise ValueError('upstream gradient of shape %s, expected %s' % (tuple(t.shape), (B, T, w)))
+    out = torch.empty((B, T, 11), device=dev)
+    ws = torch.empty(L.glamr_traj_local_to_global_backward_workspace_bytes(B, T), dtype=torch.uint8, device=dev)
+    _lib.check(L.glamr_traj_local_to_global_backward(B, T, _lib.ptr(lens), _lib.ptr(local_traj), _lib.ptr(g[0]), _lib.ptr(g[1]), _lib.ptr(g[2]), _lib.ptr(out),
+                                                     _lib.ptr(ws), _lib.current_stream()))
+    return out

@@ -230,6 +230,25 @@ int glamr_nets_traj_clip(glamr_nets* h, int n_seq, int T, int mode, const glamr_
 size_t glamr_traj_local_to_global_workspace_bytes(int n_seq, int T);
 int glamr_traj_local_to_global(int n_seq, int T, const float* local_traj, float* out_trans, float* out_orient, float* out_orient_q,
                                void* workspace, void* stream);
+/* The vector-Jacobian product of glamr_traj_local_to_global: of traj_local2global_heading (traj_utils.py:65-88, local_heading=True, 6D
+ * local orientation: vec_to_heading :69, the heading's cumsum :71, heading_to_quat :74, rot_2d of rows 1.. by the PREVIOUS row's heading
+ * :75-76, the displacement's cumsum :77, rot6d_to_quat :80, the two quat_mul :86-87) followed by quaternion_to_angle_axis
+ * (konia_transform.py:560-630), with the reference's epsilon placement and `where` branches (csrc/rotmath.hpp).  For upstream gradients
+ * g_trans (n_seq, T, 3), g_orient (axis-angle output, n_seq, T, 3) and g_orient_q (quaternion output, n_seq, T, 4) -- each may be NULL, at
+ * least one is given, the given ones add up -- it writes g_local_traj (n_seq, T, 11) = dL/d local_traj.  Nothing is taped: the headings are
+ * recomputed from local_traj, which must be what the forward was given.  lens_dev: DEVICE table (n_seq) of frames per sequence, NULL = T
+ * everywhere; an entry is clamped to [0, T].  Rows at or beyond a sequence's length are never read from the upstream arrays (they may hold
+ * NaN) and are written as zeros.  (The forward itself always runs over T rows; a row's outputs depend on the rows before it only.)
+ * One workgroup of 256 threads per sequence, any T; no atomics and a fixed summation order: two calls give the same bits.  Plain fp32:
+ * the result is linear in the upstream gradients to rounding.  After its argument checks the call reads no host memory and does not
+ * synchronise: it can be recorded into a stream capture.  workspace: glamr_traj_local_to_global_backward_workspace_bytes (16 bytes per
+ * frame), device memory, contents irrelevant before and after. */
+size_t glamr_traj_local_to_global_backward_workspace_bytes(int n_seq, int T);
+int glamr_traj_local_to_global_backward(int n_seq, int T, const int32_t* lens_dev /* (n_seq) DEVICE, or NULL = T */,
+                                        const float* local_traj /* (n_seq,T,11), what the forward was given */,
+                                        const float* g_trans /* (n_seq,T,3) or NULL */, const float* g_orient /* axis-angle, (n_seq,T,3) or NULL */,
+                                        const float* g_orient_q /* (n_seq,T,4) or NULL */, float* g_local_traj /* out (n_seq,T,11) */,
+                                        void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * Fused global optimiser -- replaces GlobalReconOptimizer.forward/compute_loss/optimize_main
