@@ -26,7 +26,7 @@ from ...lib.utils import np_transform as nt
 from ...models import latent_rng
 from ...models.prior_models import MotionTrajJointModel
 from ...models.priors import num_windows, NZ
-from .. import packing
+from .. import packing, stepwise
 from ..configs import get_config
 
 # (body26fk index, smpl index) pairs with identical joint names (lib/utils/joints.py:48-73,619-641 through :82-85): the 14
@@ -1018,16 +1018,13 @@ class GlobalReconOptimizer:
         events = []
         want_hist = (self.log is not None or self.keep_loss_history) and not torch.cuda.is_current_stream_capturing()
         for stage, spec in self.opt_stage_specs.items():
-            sd = packing.stage_desc(spec, self.specs, has_world_dheading=has_wd,
-                                    niters=None if max_iters is None else min(max_iters, spec['opt_niters']))
+            sd = packing.stage_desc(spec, self.specs, has_world_dheading=has_wd, niters=stepwise.stage_iters(spec, max_iters))
             if want_hist and sd.niters > 0:
                 packed.t['loss_history'] = torch.zeros((packed.S, int(sd.niters), len(packing.LOSS_IDS)), dtype=torch.float32, device=self.device)
             events.append(self._run(packed, sd))               # the launch's workspace: its header carries the kernel's own clock stamps
             if 'loss_history' in packed.t:
                 self._report_stage(packed, stage, spec, packed.t.pop('loss_history'), events[-1])
-            has_wd = has_wd or 'world_dheading' in spec['opt_variables']
-            if spec.get('reinitialize_cam', False):
-                packed.t['cam_pose'][:] = packed.t['cam_pose'][:, :1]
+            has_wd = stepwise.end_stage(packed, spec, has_wd)
         packed.has_world_dheading = has_wd
         packed.stage_ws = events
         return packed
@@ -1181,232 +1178,11 @@ class GlobalReconOptimizer:
         return self.flag_opt_motion_latent or self.flag_opt_traj_latent
 
     def run_latent_schedule(self, rin, packed, max_iters=None):
-        """The staged optimisation in LATENT-OPTIMISATION mode (flag_opt_motion_latent / flag_opt_traj_latent; :155-158,434-437,619-622).
-        Every iteration from `opt_latent_start_iter` on re-runs infer_motion_traj with the current latents (:352-392): the infiller's output
-        becomes `smpl_pose`, the trajectory predictor's local trajectory the new `traj_local_pred`, and SMPL gives new joints; the loss
-        reaches `motion_latent` through the reprojection term -> joints -> SMPL (body pose) -> infiller (all windows, autoregressively).
-        `traj_latent` is in the parameter list but never receives a gradient: get_pred_trajectory_base detaches traj_local_pred (:396), and
-        torch.optim.Adam skips a parameter whose grad is None -- its value stays, exactly as in the reference.
-        Per iteration over the C ABI: taped infiller (glamr_nets_infill_taped), trajectory predictor (glamr_nets_infer), joints-only
-        skinning, one gradient launch of the stage kernel (niters 1, lr 0, grads_out, g_j_local), glamr_smpl_backward, glamr_nets_infill_backward,
-        glamr_adam_step_indexed on the scene parameters and on the latents (torch.optim.Adam's arithmetic; a parameter's step count advances only
-        when it has a gradient: two indices on the device).  The first two iterations of a stage are plain launches; the third is CAPTURED as a HIP
-        graph and the rest of the stage replays it (GLAMR_LATENT_GRAPH=0: plain launches throughout; self.latent_graph_replays counts)."""
-        import ctypes
-        from ... import parallel
-        dev, L = self.device, _lib.lib()
-        S, P, T = packed.S, packed.P, packed.T
-        n_slots = S * P
-        meps, teps = packed.latents
-        meps, teps = meps.clone(), teps.clone()
-        pa = packed.person_arrays
-        h = self.mt_model.handle
-        attach = self.flag_attach_traj_pred
-        tape_gb = (L.glamr_nets_tape_bytes(h.h, n_slots, T) + (L.glamr_nets_traj_tape_bytes(h.h, n_slots, T) if attach else 0)) / 2.0 ** 30
-        if tape_gb > 96:
-            raise ValueError('latent-optimisation mode keeps every activation of the infiller (and of the attached trajectory predictor) for its backward: %.0f GB for %d person slots of %d frames; '
-                             'run it on smaller batches (the reference runs it on one sequence at a time)' % (tape_gb, n_slots, T))
-        lens = np.ascontiguousarray(rin.lens, dtype=np.int32)
-        fr_start = packed.t['fr_start'].cpu().numpy()
-        occupied = rin.seq_len_slot.cpu().numpy() > 0                    # (person slots a scene with fewer persons leaves empty are skipped)
-        # frame rows of the priors' outputs (row e of slot k = video frame fr_start[k] + e) <-> the per-slot video-frame arrays: ONE gather /
-        # scatter index for the whole batch instead of a python loop over the slots, twice per iteration
-        src, dst = [], []
-        for k in range(n_slots):
-            if occupied[k]:
-                nk, fs = int(lens[k]), int(fr_start[k])
-                src.append(k * T + np.arange(nk))
-                dst.append(k * T + fs + np.arange(nk))
-        src = torch.as_tensor(np.concatenate(src) if src else np.zeros(0, np.int64), device=dev)
-        dst = torch.as_tensor(np.concatenate(dst) if dst else np.zeros(0, np.int64), device=dev)
-        smpl_h = self.smpl._handle(dev)
-        zeros3 = torch.zeros((n_slots * T, 3), device=dev)
-        packed.t['g_j_local'] = torch.zeros((n_slots, T, packing.NJ, 3), device=dev)
-        if attach:
-            # dL/d traj_local_pred of the gradient launch, rows in the priors' own order (traj_local_pred is stored by existing-frame row);
-            # the predictor takes lengths >= 1: an empty slot runs as one frame whose gradient rows are zero
-            g_traj_local = torch.zeros((n_slots, T, 11), device=dev)
-            lens_t = np.maximum(lens, 1).astype(np.int32)
-        params = packed.t['params']
-        m_lat, v_lat = torch.zeros_like(meps), torch.zeros_like(meps)
-        m_tl, v_tl = torch.zeros_like(teps), torch.zeros_like(teps)      # traj_latent's own moments (attached mode only)
-        extra = {}
-        m, v = torch.zeros_like(params), torch.zeros_like(params)
-        step_idx = torch.zeros(3, dtype=torch.int32, device=dev)         # [0] scene parameters, [1] motion latents, [2] trajectory latents: 0-based row of the coefficient table
-        # the latent regularisers (glamr_latent_reg, DESIGN.md 13): per-slot window counts (0 = an empty slot) on the host for the argument checks
-        # and on the device for the kernel, the gradient arrays of a latent that has no data gradient in an iteration, the values of the last launch
-        n_win_host = np.ascontiguousarray([num_windows(int(lens[k])) if occupied[k] else 0 for k in range(n_slots)], dtype=np.int32)
-        n_win_dev = torch.as_tensor(n_win_host, device=dev)
-        g_reg_m, g_reg_t = torch.zeros_like(meps), torch.zeros_like(teps)
-        reg_values = torch.zeros((S, 2), device=dev)
-        self.latent_loss_history = {}
-        has_wd = False
-        use_graph = os.environ.get('GLAMR_LATENT_GRAPH', '1') != '0'
-        self.latent_graph_replays = 0
-
-        def adam_latent(x, m_x, v_x, g, coef, idx):
-            # (a parameter's step count advances only when it has a gradient: the latents have their own indices)
-            _lib.check(L.glamr_adam_step_indexed(x.numel(), _lib.ptr(x), _lib.ptr(m_x), _lib.ptr(v_x), _lib.ptr(g), _lib.ptr(coef), _lib.ptr(step_idx[idx:]),
-                                                 _lib.current_stream()))
-            _lib.check(L.glamr_counter_add(_lib.ptr(step_idx[idx:]), 1, _lib.current_stream()))
-
-        def iteration(spec, with_priors, first, coef, regs=None, hist=None):
-            """One Adam iteration (:547-570 in latent mode), launches only -- nothing here reads a value back or depends on the iteration
-            number except through `step_idx` on the device, so the same launch sequence is captured ONCE per stage and replayed."""
-            tape = ttape = None
-            if with_priors:
-                # infer_motion_traj with the current latents (:352-392)
-                pose_out, tape = h.infill_taped(pa['nets_pose'], pa['nets_vis'], lens, meps)
-                if attach:      # the same predictor with its activations kept (the rows are bit-identical, DESIGN.md 11)
-                    local_traj, ttape = h.traj_taped(lens_t, teps, in_body_pose=pose_out)
-                    tr = {'local_traj': local_traj}
-                else:
-                    tr = h.infer(pose_out, None, lens, traj_eps=teps, infill=False, traj=True)
-                pa['smpl_pose'].view(-1, 69).index_copy_(0, dst, pose_out.view(-1, 69).index_select(0, src))
-                packed.t['traj_local_pred'].view(-1, 11).index_copy_(0, src, tr['local_traj'].view(-1, 11).index_select(0, src))
-                with torch.no_grad():
-                    jl = self.smpl(global_orient=zeros3, body_pose=pa['smpl_pose'].view(-1, 69), betas=pa['smpl_beta'].view(-1, 10), root_trans=zeros3,
-                                   return_verts=False).joints
-                if packed.t['j_local'].shape == (n_slots, T, packing.NJ, 3):
-                    packed.t['j_local'].copy_(jl.view(n_slots, T, packing.NJ, 3))          # (a fixed address: the gradient launch below is captured with it)
-                else:
-                    packed.t['j_local'] = jl.view(n_slots, T, packing.NJ, 3).clone()
-            sd = packing.stage_desc(spec, self.specs, has_wd, niters=1)
-            sd.lr = 0.0
-            if not first:
-                sd.flags |= packing.FLAG_KEEP_CAM_PARAMS
-            # (only a launch whose priors ran has a reader for dL/d traj_local_pred: before opt_latent_start_iter the usual instance runs)
-            packed.t['g_traj_local'] = g_traj_local if ttape is not None else None
-            grads = parallel._device_run_stage(packed, sd, True)
-            g_lat = g_bp = None
-            if ttape is not None:
-                # dL/d traj_local_pred -> trajectory latent, and -> joint rows -> body pose (the FK step in reverse) for the motion latent
-                g_tl, g_joints = h.traj_backward(ttape, g_traj_local, want_joints=self.flag_opt_motion_latent)
-                extra['g_traj_latent'] = g_tl
-                if g_joints is not None:
-                    g_bp = h.fk_backward(pose_out, lens_t, g_joints)
-                if self.flag_opt_traj_latent and regs is None:
-                    adam_latent(teps, m_tl, v_tl, g_tl, coef, 2)
-            if tape is not None and self.flag_opt_motion_latent:
-                # dL/d j_local -> body pose (skinning, blend shapes, chain, re-anchoring in reverse) -> latents (all windows)
-                pose72 = torch.cat([zeros3, pa['smpl_pose'].view(-1, 69)], dim=1).contiguous()
-                g_pose = torch.empty((n_slots * T, 72), device=dev)
-                ws = torch.empty(L.glamr_smpl_backward_workspace_bytes(smpl_h, n_slots * T, 0), dtype=torch.uint8, device=dev)
-                _lib.check(L.glamr_smpl_backward(smpl_h, n_slots * T, _lib.ptr(pose72), _lib.ptr(pa['smpl_beta'].view(-1, 10)), _lib.ptr(zeros3), None, None, None,
-                                                 None, _lib.ptr(packed.t['g_j_local']), _lib.ptr(g_pose), None, None, None, 0, _lib.ptr(ws), _lib.current_stream()))
-                g_out = torch.zeros((n_slots * T, 69), device=dev)
-                g_out.index_copy_(0, src, g_pose[:, 3:].index_select(0, dst))
-                if g_bp is not None:
-                    g_out += g_bp.view(-1, 69)
-                g_lat = h.infill_backward(tape, g_out.view(n_slots, T, 69))
-                if regs is None:
-                    adam_latent(meps, m_lat, v_lat, g_lat, coef, 1)
-            if regs is not None:
-                # A stage with a latent regulariser (compute_loss :533-545 evaluates it in EVERY iteration, also before opt_latent_start_iter): one
-                # launch for both latents, at the latents this iteration started from.  A latent that has a data gradient gets the regulariser's
-                # ADDED to it, one that has none gets it STORED -- and is stepped by it alone (traj_latent in detached mode; both latents before
-                # opt_latent_start_iter, when the priors are not re-run).  One Adam step per latent that has any gradient.
-                (w_m, mode_m), (w_t, mode_t) = regs
-                g_t_data = extra.get('g_traj_latent') if (ttape is not None and self.flag_opt_traj_latent) else None
-                g_m = g_lat if g_lat is not None else g_reg_m
-                g_t = g_t_data if g_t_data is not None else g_reg_t
-                _lib.check(L.glamr_latent_reg(S, P, meps.shape[1], _lib.ptr(meps), _lib.ptr(teps), _lib.ptr(n_win_dev), _lib.ptr(n_win_host), w_m, w_t, mode_m, mode_t,
-                                              int(g_lat is not None), int(g_t_data is not None), _lib.ptr(g_m), _lib.ptr(g_t), _lib.ptr(reg_values),
-                                              _lib.ptr(hist), 0 if hist is None else hist.shape[1], _lib.ptr(step_idx), _lib.current_stream()))
-                if g_t_data is not None or mode_t == _lib.LATENT_REG_ACTIVE:
-                    extra['g_traj_latent_total'] = g_t
-                    adam_latent(teps, m_tl, v_tl, g_t, coef, 2)
-                else:
-                    extra.pop('g_traj_latent_total', None)
-                if g_lat is not None or mode_m == _lib.LATENT_REG_ACTIVE:
-                    extra['g_motion_latent_total'] = g_m
-                    adam_latent(meps, m_lat, v_lat, g_m, coef, 1)
-                else:
-                    extra.pop('g_motion_latent_total', None)
-            _lib.check(L.glamr_adam_step_indexed(params.numel(), _lib.ptr(params), _lib.ptr(m), _lib.ptr(v), _lib.ptr(grads), _lib.ptr(coef), _lib.ptr(step_idx),
-                                                 _lib.current_stream()))
-            _lib.check(L.glamr_counter_add(_lib.ptr(step_idx), 1, _lib.current_stream()))
-            return g_lat
-
-        for stage, spec in self.opt_stage_specs.items():
-            n = spec['opt_niters'] if max_iters is None else min(max_iters, spec['opt_niters'])
-            start = spec.get('opt_latent_start_iter', 0)                 # optimize() :581
-            # init_opt creates a fresh optimiser per stage (:635-644): zero moments, step counts back to the first row of the stage's table
-            m.zero_(); v.zero_(); m_lat.zero_(); v_lat.zero_(); m_tl.zero_(); v_tl.zero_(); step_idx.zero_()
-            tab = np.empty(2 * max(n, 1), np.float32)
-            _lib.check(L.glamr_adam_coef_table(float(spec['opt_lr']), max(n, 1), tab.ctypes.data_as(ctypes.c_void_p)))
-            coef = torch.as_tensor(tab, device=dev)
-            # the latent regularisers are this loop's, not the stage kernel's: the launch gets the loss_cfg without them
-            rest_cfg, regs = packing.split_latent_regs(spec['loss_cfg'])
-            hist = None
-            if any(mode != _lib.LATENT_REG_ABSENT for _, mode in regs):
-                spec = dict(spec, loss_cfg=rest_cfg)
-                hist = torch.zeros((S, max(n, 1), 2), device=dev)
-            else:
-                regs = None                                              # (no regulariser: today's launch sequence, launch for launch)
-            graph = None
-            for it in range(n):
-                with_priors = it >= start
-                if graph is not None:
-                    graph.replay()
-                    self.latent_graph_replays += 1
-                    continue
-                g_lat = iteration(spec, with_priors, it == 0, coef, regs, hist)
-                trace = getattr(self, 'latent_trace', None)
-                if regs is not None and trace is not None and 'latent_reg' not in trace:      # the two values of the run's first regularised iteration
-                    trace['latent_reg'] = reg_values.detach().cpu().numpy()
-                if (g_lat is not None or (with_priors and (attach or regs is not None))) and trace is not None and 'losses' not in trace:      # first gradient of the run, for the parity tests
-                    self.latent_trace.update(losses=packed.t['losses'].detach().cpu().numpy(),
-                                             smpl_pose=pa['smpl_pose'].detach().cpu().numpy(), traj_local_pred=packed.t['traj_local_pred'].detach().cpu().numpy())
-                    if g_lat is not None:
-                        self.latent_trace['g_motion_latent'] = g_lat.detach().cpu().numpy()
-                    if attach:
-                        self.latent_trace.update(g_traj_latent=extra['g_traj_latent'].detach().cpu().numpy(),
-                                                 g_traj_local=g_traj_local.detach().cpu().numpy())
-                    elif 'g_traj_latent_total' in extra:                  # detached mode: the regulariser is traj_latent's whole gradient
-                        self.latent_trace['g_traj_latent'] = extra['g_traj_latent_total'].detach().cpu().numpy()
-                # from here on every iteration of the stage is the same launch sequence: capture it once, replay it n - it - 2 times
-                if use_graph and with_priors and it >= 1 and n - it - 1 >= 2 and not torch.cuda.is_current_stream_capturing():
-                    try:
-                        g = torch.cuda.CUDAGraph()
-                        cur = torch.cuda.current_stream(dev)
-                        side = self.__dict__.setdefault('_latent_capture_stream', torch.cuda.Stream(device=dev))
-                        side.wait_stream(cur)
-                        with torch.cuda.graph(g, stream=side):
-                            iteration(spec, True, False, coef, regs, hist)
-                        cur.wait_stream(side)
-                        graph = g
-                    except Exception as e:      # noqa: BLE001 -- the plain launches are always available
-                        import sys
-                        sys.stderr.write('latent-optimisation mode: iteration graph not used (%s); plain launches\n' % e)
-                        torch.cuda.synchronize(dev)
-                        graph, use_graph = None, False
-            has_wd = has_wd or 'world_dheading' in spec['opt_variables']
-            if spec.get('reinitialize_cam', False):
-                packed.t['cam_pose'][:] = packed.t['cam_pose'][:, :1]
-            del graph
-            if hist is not None:
-                self._report_latent_stage(packed, stage, spec, regs, hist[:, :n])
-        packed.has_world_dheading = has_wd
-        packed.stage_ws = []
-        packed.latents = (meps, teps)
-        packed.t['g_j_local'] = None
-        packed.t['g_traj_local'] = None
-        return packed
-
-    def _report_latent_stage(self, packed, stage, spec, regs, hist):
-        """latent_loss_history[stage] and, with a `log`, write_logs' line (:646-659) per iteration for the stage's latent regularisers under the
-        reference's names (the unweighted values, loss_uw_dict :564).  The latent-optimisation schedule records no other term per iteration."""
-        h = hist.cpu().numpy()                                          # (waits for the stage)
-        self.latent_loss_history[stage] = h
-        if self.log is None:
-            return
-        names = [(t, n) for t, n in enumerate(packing.LATENT_REG_TERMS) if regs[t][1] != _lib.LATENT_REG_ABSENT]
-        seqs = getattr(packed, 'seq_names', None) or ['seq%d' % si for si in range(packed.S)]
-        for si in range(packed.S):
-            for it in range(h.shape[1]):
-                loss_str = ' | '.join('%s: %7.3f' % (n, h[si, it, t]) for t, n in names)
-                self.log.info('%s - %s - %s | %4d/%d | LR: %.0e | %s' % (self.cfg_id, seqs[si], stage, it, h.shape[1], spec['opt_lr'], loss_str))
+        """The staged optimisation in LATENT-OPTIMISATION mode (flag_opt_motion_latent / flag_opt_traj_latent): the priors run inside the Adam loop
+        and the latent draws are parameters -- launch by launch, from the third iteration of a stage on as replays of one captured HIP graph
+        (latent_schedule.LatentSchedule; GLAMR_LATENT_GRAPH=0: plain launches throughout; self.latent_graph_replays counts)."""
+        from ..latent_schedule import LatentSchedule
+        return LatentSchedule(self, rin, packed).run(max_iters)
 
     def collect(self, datas, packed, fetched=None):
         """Device arrays -> the reference's output dictionaries (numpy): one device->host copy per array.  Waits for this batch only."""

@@ -22,7 +22,7 @@ FLAG_NO_REPORT = 128                                       # launch-by-launch sc
 FLAG_ABSOLUTE_HEADING = 64                                 # specs absolute_heading: per-frame headings are absolute (csrc/grecon_wide.hip instances)
 
 # The latent regularisers (loss_func.py:293-310), in the order of glamr_latent_reg's terms, with the flag that makes each one's
-# latent an Adam parameter.  They are NOT terms of the fused stage kernel (stage_desc refuses them): run_latent_schedule takes them itself.
+# latent an Adam parameter.  They are NOT terms of the fused stage kernel (stage_desc refuses them): latent_schedule.LatentSchedule takes them itself.
 LATENT_REG_TERMS = {'motion_latent_reg': 'flag_opt_motion_latent', 'traj_latent_reg': 'flag_opt_traj_latent'}
 
 

@@ -1,0 +1,65 @@
+"""What the launch-by-launch schedules share (latent_schedule.LatentSchedule, parallel.PersonShardedSchedule; stage_iters / end_stage also
+GlobalReconOptimizer.run_schedule): a stage's iteration count and epilogue, the gradient launch's descriptor, torch.optim.Adam's step with
+its step number on the device, and the capture of one iteration as a HIP graph."""
+import numpy as np
+import torch
+
+from .. import _lib
+from . import packing
+
+
+def stage_iters(spec, max_iters):
+    """Iterations of a stage: `max_iters` caps the configured count (tests); None = the configured schedule."""
+    return spec['opt_niters'] if max_iters is None else min(max_iters, spec['opt_niters'])
+
+
+def end_stage(packed, spec, has_wd):
+    """After a stage's last iteration: reinitialize_cam (the first frame's camera for every frame); returns `has_wd` for the stages that
+    follow -- the world heading offset is applied whenever the variable exists (:459-465), from the first stage that optimises it on."""
+    if spec.get('reinitialize_cam', False):
+        packed.t['cam_pose'][:] = packed.t['cam_pose'][:, :1]
+    return has_wd or 'world_dheading' in spec['opt_variables']
+
+
+def grad_launch_desc(spec, model_specs, has_wd, first, extra_flags=0):
+    """The stage descriptor of a GRADIENT launch: one iteration with lr 0 (the caller makes the update from grads_out).  Only a stage's
+    `first` launch sets the camera parameters from cam_pose; every later one keeps what the optimiser made of them."""
+    sd = packing.stage_desc(spec, model_specs, has_wd, niters=1)
+    sd.lr = 0.0
+    sd.flags |= (0 if first else packing.FLAG_KEEP_CAM_PARAMS) | extra_flags
+    return sd
+
+
+class IndexedAdam:
+    """torch.optim.Adam's arithmetic for the `n` iterations of a stage with the step NUMBER on the device, so that a captured iteration steps
+    on at every replay: the host-made coefficient table (glamr_adam_coef_table) and one int32 counter per `slot` -- the 0-based row of the
+    table a parameter group is at (a group's count advances only when it is stepped, as a parameter's whose grad is None does not)."""
+
+    def __init__(self, lr, n, device, slots=1):
+        n = max(int(n), 1)
+        tab = np.empty((n, 2), np.float32)
+        _lib.check(_lib.lib().glamr_adam_coef_table(float(lr), n, _lib.ptr(tab)))
+        self.coef = torch.from_numpy(tab).to(device)
+        self.counters = torch.empty(slots, dtype=torch.int32, device=device)
+        self.reset()
+
+    def reset(self):
+        self.counters.zero_()
+
+    def step(self, x, m, v, g, slot=0):
+        """x, m, v <- one Adam step with gradient g at the slot's row of the table; the slot's counter + 1 (current stream)."""
+        L, idx, st = _lib.lib(), _lib.ptr(self.counters[slot:]), _lib.current_stream()
+        _lib.check(L.glamr_adam_step_indexed(x.numel(), _lib.ptr(x), _lib.ptr(m), _lib.ptr(v), _lib.ptr(g), _lib.ptr(self.coef), idx, st))
+        _lib.check(L.glamr_counter_add(idx, 1, st))
+
+
+def capture_iteration(fn, device, side_stream, capture_error_mode=None):
+    """The launches of fn() as a HIP graph: captured on `side_stream`, which joins the current stream before and is joined by it after.
+    Nothing runs; the caller replays the graph.  Whatever the capture raises is the caller's to handle."""
+    graph = torch.cuda.CUDAGraph()
+    cur = torch.cuda.current_stream(device)
+    side_stream.wait_stream(cur)
+    with torch.cuda.graph(graph, stream=side_stream, **({} if capture_error_mode is None else {'capture_error_mode': capture_error_mode})):
+        fn()
+    cur.wait_stream(side_stream)
+    return graph

@@ -162,6 +162,7 @@ class PersonShardedSchedule:
         self.grad_hook = grad_hook
         self.collective_seconds = 0.0
         self.launches = 0
+        self._side_stream = None                  # the stream the iteration graphs are captured on (made at the first capture)
 
     def owned(self, n_persons):
         lo, hi = shard_range(n_persons, self.rank, self.world)
@@ -199,7 +200,7 @@ class PersonShardedSchedule:
     def run(self, packed, opt_stage_specs, model_specs, max_iters=None, has_wd=False):
         """Runs the whole schedule on `packed` (the FULL scene batch, identical on every rank when the call starts).  On return every rank
         holds the full result: parameters, world poses and projections of all persons, the camera."""
-        from .global_recon import packing
+        from .global_recon import packing, stepwise
         S, P, T, l = packed.S, packed.P, packed.T, packed.layout
         if P < self.world:
             raise ValueError('%d persons cannot be sharded over %d ranks' % (P, self.world))
@@ -213,7 +214,7 @@ class PersonShardedSchedule:
         for stage, spec in opt_stage_specs.items():
             if model_specs.get('flag_opt_cam_from_person_pose', False) and 'cam' not in spec['opt_variables']:
                 raise NotImplementedError('stage %r derives the camera from the persons: not covered by the person-sharded exchange' % stage)
-            n = spec['opt_niters'] if max_iters is None else min(max_iters, spec['opt_niters'])
+            n = stepwise.stage_iters(spec, max_iters)
             m, v = torch.zeros_like(params), torch.zeros_like(params)
             not_own = [pi for pi in range(P) if pi not in own]
             grad_ws = None
@@ -229,9 +230,9 @@ class PersonShardedSchedule:
                 fwd.flags |= keep | packing.FLAG_POSES_ONLY                         # (only the world poses are wanted: no residuals, no projections)
                 self.run_stage(packed, fwd, False)                                   # 1. own poses at the current parameters (+ camera parameters at it 0)
                 self._all_gather_poses(packed, own, block)                           # 2.
-                gd = packing.stage_desc(spec, model_specs, has_wd, niters=1)
-                gd.lr = 0.0                                                          # the update is made below, after the reduction
-                gd.flags |= packing.FLAG_KEEP_CAM_PARAMS | (packing.FLAG_NO_CAMERA_TERMS if self.rank != 0 else 0) | (0 if report else packing.FLAG_NO_REPORT)
+                # (lr 0: the update is made below, after the reduction; the forward-only launch has already set the camera parameters)
+                gd = stepwise.grad_launch_desc(spec, model_specs, has_wd, first=False,
+                                               extra_flags=(packing.FLAG_NO_CAMERA_TERMS if self.rank != 0 else 0) | (0 if report else packing.FLAG_NO_REPORT))
                 if grad_ws is not None:
                     # the gradient launches of a stage share ONE workspace nothing else writes to: from the second on, the stage-constant tables of
                     # the set-up are still in it (GLAMR_FLAG_KEEP_TABLES: ~100 us of a 250 us launch)
@@ -254,9 +255,7 @@ class PersonShardedSchedule:
             if graph is None:
                 for it in range(n):
                     iteration(it, lambda g, it=it: self.adam_step(params.view(-1), m.view(-1), v.view(-1), g.view(-1), spec['opt_lr'], it + 1), report=(it == n - 1))
-            has_wd = has_wd or 'world_dheading' in spec['opt_variables']
-            if spec.get('reinitialize_cam', False):
-                packed.t['cam_pose'][:] = packed.t['cam_pose'][:, :1]
+            has_wd = stepwise.end_stage(packed, spec, has_wd)
         # every rank ends with the whole scene: own persons' variables and outputs to everybody -- including the BASE poses of the persons it
         # did not own (during the loop those slots carried the peers' world poses: _all_gather_poses) and the loss values of the whole scene
         self._share_results(packed, own, block, person_cols)
@@ -281,29 +280,18 @@ class PersonShardedSchedule:
         knob = os.environ.get('GLAMR_SHARDED_GRAPH', '1' if self.world <= 1 else '0')
         if self.run_stage is not _device_run_stage or self.adam_step is not _device_adam_step or not params.is_cuda or knob == '0':
             return None
-        import ctypes
-        import numpy as np
-        from . import _lib
-        L = _lib.lib()
-        tab = np.zeros((n, 2), np.float32)
-        _lib.check(L.glamr_adam_coef_table(ctypes.c_double(float(lr)), int(n), _lib.ptr(tab)))
-        tab_d = torch.from_numpy(tab).to(params.device)
-        step = torch.zeros(1, dtype=torch.int32, device=params.device)
-
-        def adam_indexed(g):
-            st = _lib.current_stream()
-            _lib.check(L.glamr_adam_step_indexed(params.numel(), _lib.ptr(params), _lib.ptr(m), _lib.ptr(v), _lib.ptr(g), _lib.ptr(tab_d), _lib.ptr(step), st))
-            _lib.check(L.glamr_counter_add(_lib.ptr(step), 1, st))
+        from .global_recon import stepwise
+        adam = stepwise.IndexedAdam(lr, n, params.device)
+        adam_indexed = lambda g: adam.step(params, m, v, g)
         snapshot = (params.clone(), m.clone(), v.clone(), self.launches)
         try:
             iteration(0, adam_indexed, report=False)
             iteration(1, adam_indexed, report=False)                                # (a plain iteration of the captured kind first: allocations, attribute calls)
             torch.cuda.synchronize(params.device)
-            g = torch.cuda.CUDAGraph()
-            side = torch.cuda.Stream(device=params.device)
-            side.wait_stream(torch.cuda.current_stream(params.device))
-            with torch.cuda.graph(g, stream=side, capture_error_mode='thread_local'):
-                iteration(2, adam_indexed, report=False)                            # (iteration number only selects KEEP_CAM_PARAMS: any it > 0 is the same graph)
+            if self._side_stream is None:
+                self._side_stream = torch.cuda.Stream(device=params.device)
+            # (the iteration number only selects KEEP_CAM_PARAMS: any it > 0 is the same graph)
+            g = stepwise.capture_iteration(lambda: iteration(2, adam_indexed, report=False), params.device, self._side_stream, 'thread_local')
             self.launches -= 2                                                      # (capturing launched nothing)
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()

@@ -208,3 +208,43 @@ def test_keypoint_count_filter_with_the_reference_default_removes_every_frame(go
     opt.make_invis_keypoint_min_score, opt.make_invis_keypoint_min_num = 0.6, 15
     d = opt._person_arrays(in_dict['est'][0])
     assert np.array_equal(d['visible'], g['kp_default_visible']) and np.array_equal(d['vis_frames'], g['kp_default_vis_frames']) and not d['vis_frames'].any()
+
+
+@pytest.mark.parametrize('lens,fr_start,occupied', [
+    ([17, 9, 30, 1], [0, 5, 3, 29], [True, True, True, True]),          # two scenes x two person slots, ragged starts and lengths
+    ([17, 0, 30, 12], [0, 0, 3, 20], [True, False, True, True]),        # one empty slot in the middle
+    ([0, 0, 0, 0], [0, 0, 0, 0], [False, False, False, False]),         # a batch whose slots are all empty
+])
+def test_frame_row_index_equals_the_per_slot_loop(lens, fr_start, occupied):
+    from glamr_amd.global_recon.latent_schedule import frame_row_index
+    T = 32
+    src, dst = frame_row_index(np.asarray(lens, np.int32), np.asarray(fr_start, np.int32), np.asarray(occupied), T)
+    want_src, want_dst = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
+    for k in range(len(lens)):
+        if occupied[k]:
+            want_src.append(k * T + np.arange(lens[k]))
+            want_dst.append(k * T + fr_start[k] + np.arange(lens[k]))
+    assert src.dtype == dst.dtype == np.int64
+    assert np.array_equal(src, np.concatenate(want_src)) and np.array_equal(dst, np.concatenate(want_dst))
+    assert len(src) == sum(n for n, o in zip(lens, occupied) if o) and (len(dst) == 0 or dst.max() < len(lens) * T)
+
+
+def test_stage_iters_and_end_stage():
+    """What every schedule does around a stage: the max_iters cap; has_wd turns true with the first stage that optimises world_dheading and
+    stays; reinitialize_cam gives every frame the camera of frame 0."""
+    import types
+    from glamr_amd.global_recon import stepwise
+    spec = {'opt_niters': 10, 'opt_variables': ['cam', 'local_xy']}
+    assert [stepwise.stage_iters(spec, k) for k in (None, 4, 10, 25)] == [10, 4, 10, 10]
+    cam = torch.arange(2 * 3 * 16, dtype=torch.float32).view(2, 3, 4, 4)
+    packed = types.SimpleNamespace(t={'cam_pose': cam.clone()})
+    stages = [spec, dict(spec, opt_variables=['world_dheading', 'cam']), dict(spec, reinitialize_cam=True)]
+    has_wd, seen = False, []
+    for s in stages:
+        kept = packed.t['cam_pose'].clone()
+        has_wd = stepwise.end_stage(packed, s, has_wd)
+        seen.append(has_wd)
+        want = cam[:, :1].expand_as(cam) if s.get('reinitialize_cam', False) else kept
+        assert torch.equal(packed.t['cam_pose'], want)
+    assert seen == [False, True, True]
+    assert stepwise.end_stage(packed, spec, True) is True
