@@ -16,6 +16,11 @@
 // Every per-frame operator is rotmath.hpp's.  Frame t is handled by thread t mod nthreads in every phase and writes only its own elements
 // (the dR/dh term of row t + 1 is computed by frame t, which reads row t + 1); every sum is one of the four scans: no atomics, a fixed order.
 // Rows at or beyond n are never read from the upstream arrays and are written as zeros.
+//
+// Optional world heading offset (the optimiser's world_dheading step, global_recon_model.py:459-465): with `wdh` given, g_orient
+// is the gradient of  aa(q_z(wdh[t]) (x) aa_to_quat(orient_t))  instead of orient_t: it is taken back through world_dheading_bwd first, and
+// g_wdh[t] (rows [0, n), written only where g_orient is given) receives the offset's own gradient.  The translation and g_orient_q are
+// unaffected.  Without `wdh` (the default) nothing of this is evaluated.
 #pragma once
 #include "rotmath.hpp"
 
@@ -23,9 +28,25 @@ namespace glamr {
 
 constexpr int TGB_WS_FLOATS_PER_FRAME = 4;      // h, S_x, S_y, g_h
 
-// L, gL: [T][11];  g_trans, g_orient: [T][3] or null;  g_orient_q: [T][4] or null;  ws: [4][T] floats of this sequence;  0 <= n <= T
+// out = quat_to_aa(angle_axis_to_quaternion((0, 0, w)) (x) aa_to_quat(base)) for an upstream gradient ga of `out`: returns d/dw and, with
+// g_base given, ADDS d/d base to it
+GLAMR_HD float world_dheading_bwd(const float base[3], float w, const float ga[3], float* g_base) {
+  float qz[4], qb[4], qo[4];
+  rm::heading_quat(w, qz);
+  rm::aa_to_quat(base, qb);
+  rm::quat_mul(qz, qb, qo);
+  float gqo[4] = {0.f, 0.f, 0.f, 0.f}, gqz[4] = {0.f, 0.f, 0.f, 0.f}, gqb[4] = {0.f, 0.f, 0.f, 0.f};
+  rm::quat_to_aa_bwd(qo, ga, gqo);
+  rm::quat_mul_bwd(qz, qb, gqo, gqz, g_base ? gqb : nullptr);
+  if (g_base) rm::aa_to_quat_bwd(base, gqb, g_base);
+  return rm::heading_quat_bwd(w, gqz);
+}
+
+// L, gL: [T][11];  g_trans, g_orient: [T][3] or null;  g_orient_q: [T][4] or null;  ws: [4][T] floats of this sequence;  0 <= n <= T;
+// wdh, g_wdh: [n] or null
 template <class RT>
-GLAMR_HD void traj_global_bwd(RT& rt, int n, int T, const float* L, const float* g_trans, const float* g_orient, const float* g_orient_q, float* gL, float* ws) {
+GLAMR_HD void traj_global_bwd(RT& rt, int n, int T, const float* L, const float* g_trans, const float* g_orient, const float* g_orient_q, float* gL, float* ws,
+                              const float* wdh = nullptr, float* g_wdh = nullptr) {
   const int tid = rt.tid(), nt = rt.nthreads();
   float* h = ws;
   float* Sx = ws + T;
@@ -95,7 +116,14 @@ GLAMR_HD void traj_global_bwd(RT& rt, int n, int T, const float* L, const float*
       float gq[4] = {0.f, 0.f, 0.f, 0.f};
       if (g_orient_q) for (int c = 0; c < 4; ++c) gq[c] = g_orient_q[(size_t)t * 4 + c];
       if (g_orient) {
-        const float ga[3] = {g_orient[(size_t)t * 3], g_orient[(size_t)t * 3 + 1], g_orient[(size_t)t * 3 + 2]};
+        float ga[3] = {g_orient[(size_t)t * 3], g_orient[(size_t)t * 3 + 1], g_orient[(size_t)t * 3 + 2]};
+        if (wdh) {
+          float aa[3], gb[3] = {0.f, 0.f, 0.f};
+          rm::quat_to_aa(q, aa);
+          const float gw = world_dheading_bwd(aa, wdh[t], ga, gb);
+          if (g_wdh) g_wdh[t] = gw;
+          for (int c = 0; c < 3; ++c) ga[c] = gb[c];
+        }
         rm::quat_to_aa_bwd(q, ga, gq);
       }
       float gq1[4] = {0.f, 0.f, 0.f, 0.f}, ghq[4] = {0.f, 0.f, 0.f, 0.f}, glq[4] = {0.f, 0.f, 0.f, 0.f};

@@ -1,0 +1,140 @@
+"""Caller-defined loss terms on the world poses (GlobalReconOptimizer.extra_loss): the staged optimisation launch by launch
+on the stepwise core, with a term the caller writes in torch added to every stage's total the way a non-monitor term of loss_cfg is
+(global_recon_model.py:533-545) -- what three lines in the reference's loss_func_dict do.
+
+Per iteration of a stage: (1) the gradient launch (glamr_grecon_run_stage, one iteration with lr 0 and grads_out) gives the built-in terms'
+gradient and reports the world poses at the parameters it was taken at; (2) the callback runs under torch autograd on copies of those poses;
+(3) loss.sum().backward(); (4) glamr_grecon_pose_backward adds the term's gradient, taken from the poses back to the trajectory variables,
+to the launch's gradient array; (5) one Adam step (torch.optim.Adam's arithmetic, fresh moments per stage).  Plain launches throughout: the
+callback is user Python, so nothing here is captured into a graph."""
+import ctypes
+
+import torch
+
+from .. import _lib
+from . import packing, stepwise
+
+
+def check_supported(model_specs):
+    """The model flags `extra_loss` cannot be combined with; raises ValueError naming the combination."""
+    g = model_specs.get
+    if g('flag_opt_motion_latent', False) or g('flag_opt_traj_latent', False):
+        raise ValueError('extra_loss together with the latent-optimisation mode (flag_opt_motion_latent / flag_opt_traj_latent) is not supported: '
+                         'that mode runs a schedule of its own')
+    if g('flag_opt_vis_local_rot', False):
+        raise ValueError('extra_loss together with flag_opt_vis_local_rot is not supported: the gradient mask of that flag is not applied to the term')
+    if g('absolute_heading', False):
+        raise ValueError('extra_loss together with absolute_heading is not supported: glamr_grecon_pose_backward differentiates heading increments')
+
+
+def check_not_sharded(packed):
+    """A person-sharded run (frozen person slots, or a process group of several ranks) does not exchange the term's gradient: refused."""
+    import torch.distributed as dist
+    if packed.t.get('frozen') is not None or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        raise ValueError('extra_loss together with a person-sharded run is not supported: the term would only see this rank\'s persons')
+
+
+class ExtraLossContext:
+    """What the callback is given.  orient_world / trans_world (S, P, T, 3): leaf tensors that require grad, copies of the poses the gradient
+    launch reported (axis-angle / metres, by video frame; zero on frames and slots that do not exist).  exist / vis (S, P, T) bool.
+    smpl_pose (S, P, T, 69), smpl_beta (S, P, T, 10): the body pose and shape of every frame (constants), or None when the batch was not
+    initialised on the device.  joints() (S, P, T, 26, 3) and vertices() (S, P, T, V, 3): the body model at the world poses, differentiable
+    with respect to them (glamr_smpl_backward_root), computed when called."""
+
+    def __init__(self, smpl, stage, iteration, seq_names, orient_world, trans_world, exist, vis, smpl_pose, smpl_beta):
+        self._smpl = smpl
+        self.stage, self.iteration, self.seq_names = stage, iteration, seq_names
+        self.orient_world, self.trans_world, self.exist, self.vis = orient_world, trans_world, exist, vis
+        self.smpl_pose, self.smpl_beta = smpl_pose, smpl_beta
+
+    def _body(self, verts):
+        if self.smpl_pose is None:
+            raise RuntimeError('extra_loss: joints() / vertices() need the body pose of a batch initialised on the device (default cam_fix_frames, not a continued optimisation)')
+        S, P, T = self.exist.shape
+        out = self._smpl(global_orient=self.orient_world.reshape(-1, 3), body_pose=self.smpl_pose.reshape(-1, 69), betas=self.smpl_beta.reshape(-1, 10),
+                         root_trans=self.trans_world.reshape(-1, 3), return_verts=verts)
+        return (out.vertices if verts else out.joints).view(S, P, T, -1, 3)
+
+    def joints(self):
+        return self._body(False)
+
+    def vertices(self):
+        return self._body(True)
+
+
+class ExtraLossSchedule:
+    """run_schedule with opt.extra_loss(ctx) -> (S,) tensor, one already weighted value per scene, added to every stage's total."""
+
+    def __init__(self, opt, packed, skip_term=False):
+        # skip_term: the same launches and Adam steps without steps 2-4 (what a zero term must reproduce; the timing tool's baseline)
+        self.opt, self.packed, self.skip_term = opt, packed, skip_term
+
+    def pose_backward(self, sd, g_orient, g_trans, grads, accumulate=1):
+        """glamr_grecon_pose_backward on the packed batch (current stream)."""
+        packed, L = self.packed, _lib.lib()
+        if getattr(self, '_ws', None) is None:
+            self._ws = torch.empty(L.glamr_grecon_pose_backward_workspace_bytes(packed.S, packed.P, packed.T), dtype=torch.uint8, device=packed.device)
+        sb = packed.struct()
+        _lib.check(L.glamr_grecon_pose_backward(ctypes.byref(sb), ctypes.byref(sd), _lib.ptr(g_orient), _lib.ptr(g_trans), _lib.ptr(grads), int(accumulate),
+                                                _lib.ptr(self._ws), _lib.current_stream()))
+
+    def run(self, max_iters=None, has_wd=False):
+        from .. import parallel
+        opt, packed = self.opt, self.packed
+        if opt.extra_loss is None:
+            raise ValueError('ExtraLossSchedule needs GlobalReconOptimizer.extra_loss')
+        check_supported(opt.specs)
+        check_not_sharded(packed)
+        if torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError('extra_loss runs launch by launch with user Python in every iteration and cannot be captured into a graph')
+        S, P, T = packed.S, packed.P, packed.T
+        params = packed.t['params']
+        t_idx = torch.arange(T, device=packed.device)
+        fs, fe = packed.t['fr_start'].view(S, P, 1), packed.t['fr_end'].view(S, P, 1)
+        slot_ok = torch.arange(P, device=packed.device).view(1, P, 1) < packed.t['n_persons'].view(S, 1, 1)
+        exist = (t_idx >= fs) & (t_idx < fe) & (t_idx < packed.t['seq_len'].view(S, 1, 1)) & slot_ok
+        vis = (packed.t['vis'].view(S, P, T) > 0) & slot_ok
+        pa = getattr(packed, 'person_arrays', None)
+        pose = pa['smpl_pose'].view(S, P, T, 69) if pa is not None else None
+        beta = pa['smpl_beta'].view(S, P, T, 10) if pa is not None else None
+        seq_names = getattr(packed, 'seq_names', None) or ['seq%d' % si for si in range(S)]
+        opt.extra_loss_history = {}
+        for stage, spec in opt.opt_stage_specs.items():
+            n = stepwise.stage_iters(spec, max_iters)
+            m, v = torch.zeros_like(params), torch.zeros_like(params)
+            adam = stepwise.IndexedAdam(spec['opt_lr'], n, packed.device)
+            hist = torch.zeros((S, n), dtype=torch.float32, device=packed.device)
+            for it in range(n):
+                sd = stepwise.grad_launch_desc(spec, opt.specs, has_wd, first=(it == 0))
+                grads = parallel._device_run_stage(packed, sd, True)                                  # 1.
+                if self.skip_term:
+                    adam.step(params, m, v, grads)
+                    continue
+                orient = packed.t['orient_world'].view(S, P, T, 3).clone().requires_grad_(True)
+                trans = packed.t['trans_world'].view(S, P, T, 3).clone().requires_grad_(True)
+                ctx = ExtraLossContext(opt.smpl, stage, it, seq_names, orient, trans, exist, vis, pose, beta)
+                with torch.enable_grad():
+                    loss = opt.extra_loss(ctx)                                                        # 2.
+                    if not torch.is_tensor(loss) or tuple(loss.shape) != (S,):
+                        raise ValueError('extra_loss must return a tensor of shape (%d,): one value per scene' % S)
+                    if not loss.requires_grad:
+                        raise ValueError('extra_loss returned a value that does not depend on ctx.orient_world / ctx.trans_world (no gradient): '
+                                         'a term without a gradient would be a silent zero')
+                    loss.sum().backward()                                                             # 3.
+                if orient.grad is None and trans.grad is None:
+                    raise ValueError('extra_loss returned a value that does not depend on ctx.orient_world / ctx.trans_world (grad is None)')
+                # the stage kernel applies the world heading offset as soon as the stage optimises it (the variable exists from then on, :459-465)
+                if 'world_dheading' in spec['opt_variables']:
+                    sd.flags |= packing.FLAG_HAS_WORLD_DHEADING
+                g_o = None if orient.grad is None else orient.grad.contiguous()
+                g_t = None if trans.grad is None else trans.grad.contiguous()
+                self.pose_backward(sd, g_o, g_t, grads, accumulate=1)                                 # 4.
+                if opt.extra_loss_grad_hook is not None:
+                    opt.extra_loss_grad_hook(stage, it, grads)      # (the complete gradient of the iteration, before the update)
+                adam.step(params, m, v, grads)                                                        # 5.
+                hist[:, it] = loss.detach()
+            opt.extra_loss_history[stage] = hist.cpu().numpy()
+            has_wd = stepwise.end_stage(packed, spec, has_wd)
+        packed.has_world_dheading = has_wd
+        packed.stage_ws = []
+        return packed

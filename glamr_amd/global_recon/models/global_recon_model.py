@@ -26,7 +26,7 @@ from ...lib.utils import np_transform as nt
 from ...models import latent_rng
 from ...models.prior_models import MotionTrajJointModel
 from ...models.priors import num_windows, NZ
-from .. import packing, stepwise
+from .. import extra_loss_schedule, packing, stepwise
 from ..configs import get_config
 
 # (body26fk index, smpl index) pairs with identical joint names (lib/utils/joints.py:48-73,619-641 through :82-85): the 14
@@ -218,6 +218,12 @@ class GlobalReconOptimizer:
         # would be half a million lines.
         self.keep_loss_history = False
         self.loss_history = {}
+        # extra_loss: a caller-defined term on the world poses, `extra_loss(ctx) -> (S,) tensor`, added to every stage's total.
+        # None (the default): nothing changes.  Set: optimize / optimize_batch run extra_loss_schedule.ExtraLossSchedule in place of
+        # run_schedule; extra_loss_history[stage] keeps the term's (scenes, iterations) values.
+        self._extra_loss = None
+        self.extra_loss_grad_hook = None      # hook(stage, iteration, grads): sees every iteration's complete gradient array before the Adam step
+        self.extra_loss_history = {}
         g = self.specs.get
         if g('est_type', 'hybrik') != 'hybrik' or not g('flag_infer_motion_traj', False) or not g('flag_pred_traj', True) \
                 or not g('flag_opt_traj', True) or not g('flag_infill_motion', True):
@@ -273,6 +279,27 @@ class GlobalReconOptimizer:
         self.smpl = smpl if smpl is not None else SMPL(SMPL_MODEL_DIR, pose_type='body26fk', create_transl=False).to(self.device)
         self.mt_model = mt_model if mt_model is not None else MotionTrajJointModel(None, self.device, log, smpl=self.smpl, results_root=results_root)
         self.timings = {}
+
+    @property
+    def extra_loss(self):
+        return self._extra_loss
+
+    @extra_loss.setter
+    def extra_loss(self, fn):
+        if fn is not None:
+            if not callable(fn):
+                raise TypeError('extra_loss must be callable: extra_loss(ctx) -> tensor (S,)')
+            extra_loss_schedule.check_supported(self.specs)
+        self._extra_loss = fn
+
+    def _refuse_extra_loss(self, what):
+        if self._extra_loss is not None:
+            raise NotImplementedError('%s while extra_loss is set: the term runs user Python in every iteration (optimize / optimize_batch only)' % what)
+
+    def _run_schedule_or_extra(self, packed, max_iters, has_wd=False):
+        if self._extra_loss is None:
+            return self.run_schedule(packed, max_iters, has_wd=has_wd)
+        return extra_loss_schedule.ExtraLossSchedule(self, packed).run(max_iters, has_wd=has_wd)
 
     @property
     def latent_source(self):
@@ -1082,6 +1109,7 @@ class GlobalReconOptimizer:
     def optimize_resident(self, rin, max_iters=None):
         """HBM in, HBM out: init_data + the full schedule on a ResidentInputs batch.  Returns (datas, packed) with every result
         (optimised variables, world trajectories, projections, camera) in packed.t on the device; collect() brings them to the host."""
+        self._refuse_extra_loss('optimize_resident')
         if self.latent_mode:
             datas, packed = self.init_resident(rin, init_forward=True)
             self.run_latent_schedule(rin, packed, max_iters)
@@ -1097,6 +1125,7 @@ class GlobalReconOptimizer:
         (a service loop; bench.py): a host whose driver calls are slow then no longer paces the GPU.  The step must have run once on this stream
         before (allocations, one-time attribute calls).  check=True replays once against a plain step with the same seed and requires the
         projections to agree bit for bit (RuntimeError otherwise).  Results live in graph.packed (collect() them after a replay)."""
+        self._refuse_extra_loss('capture_resident')
         if self.latent_mode:
             raise NotImplementedError('the latent-optimisation schedule captures its own graph per iteration (run_latent_schedule); the whole step is not capturable')
         # the value checks of the wire format run once per batch, outside a capture (init_resident skips them while capturing): a batch whose
@@ -1221,6 +1250,10 @@ class GlobalReconOptimizer:
         result dictionaries per batch, in order.  Software pipeline on the host thread: while the device runs batch i (asynchronous
         launches on a compute stream), the host scatters and uploads batch i + 1 (copy stream, pinned staging) and cuts the output
         dictionaries of batch i - 1 from its device->host copies (copy stream, after that batch's own event -- never a device-wide wait)."""
+        self._refuse_extra_loss('optimize_stream')
+        return self._optimize_stream(batches, latents, max_iters)
+
+    def _optimize_stream(self, batches, latents, max_iters):
         dev = self.device
         # consecutive batches alternate over two compute streams (the launch seams and tails of one batch are covered by the next, as in bench.py)
         computes = self.__dict__.setdefault('_compute_streams', [torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)])
@@ -1306,7 +1339,7 @@ class GlobalReconOptimizer:
             return self.collect(datas, packed)
         datas, packed = self.init_data_batch(in_dicts, latents, init_forward=not self._schedule_overwrites_init())
         t0 = time.time()
-        self.run_schedule(packed, max_iters)
+        self._run_schedule_or_extra(packed, max_iters)
         torch.cuda.synchronize(self.device)
         self.timings['optimise'] = time.time() - t0
         return self.collect(datas, packed)
@@ -1350,5 +1383,5 @@ class GlobalReconOptimizer:
             j_locals.append(jl)
         packed = packing.PackedScenes(datas, j_locals, self.device, self.cam_fix_frames)
         has_wd = any('world_dheading' in pd for d in datas for pd in d['person_data'].values())
-        self.run_schedule(packed, max_iters, has_wd=has_wd)
+        self._run_schedule_or_extra(packed, max_iters, has_wd=has_wd)
         return self.collect(datas, packed)

@@ -398,6 +398,36 @@ int glamr_grecon_run_stage(const glamr_scene_batch* batch, const glamr_stage_des
  * the work enqueued so far on THAT launch's stream has finished -- other streams keep running (no device-wide wait). */
 int glamr_grecon_last_launch_ns(const void* workspace, double* ns);
 
+/* Caller-defined loss terms on the world poses: the vector-Jacobian product from the poses a launch reports (orient_world, trans_world)
+ * back to the trajectory variables of `params` -- of get_pred_trajectory_base plus the world_dheading step (global_recon_model.py:394-426,
+ * 459-465), the map glamr_grecon_run_stage evaluates before its residuals.  For a person slot with existing frames [fr_start, fr_end), row e =
+ * frame fr_start + e: the assembled local row is traj_local_pred[e][0:9] + (local_xy at e = 0, local_dxy[e] otherwise | local_z[e] |
+ * local_rot[e]) with the heading vector (cos h_e, sin h_e), h_e = vec_to_heading(traj_local_pred[e][9:11]) + (local_heading at e = 0,
+ * local_dheading[e] * dheading_mask[e] otherwise; a NULL mask counts as 0); the poses are glamr_traj_local_to_global of the rows.  With
+ * GLAMR_FLAG_HAS_WORLD_DHEADING, orient_world[t] = aa(q_z(world_dheading[t]) (x) aa_to_quat(base[t])) on every frame t < seq_len, base[t] =
+ * base_orient[t] outside the existing range (where the poses are constants otherwise); the translation is unaffected.
+ * g_orient_world / g_trans_world: dev (slots, max_len, 3) upstream gradients by video frame like orient_world / trans_world, each may be
+ * NULL (at least one is given).  Rows outside a person's existing range are read only by the world_dheading rule; rows at or beyond the
+ * scene's seq_len and the arrays of empty slots are never read (they may hold NaN).
+ * grads: dev (n_scenes, scene_stride), the layout of glamr_grecon_run_stage's grads_out.  Written, for the variables of stage->var_mask only:
+ * local_xy, local_heading, local_dxy[e >= 1], local_dheading[e >= 1] (times the mask), local_z, local_rot, and world_dheading[t] when the flag
+ * is set.  accumulate != 0: the values are ADDED and every other entry is left untouched; accumulate == 0: they are stored and every other
+ * entry of the array (the camera block, variables outside the mask, rows beyond a range, empty and frozen slots) is stored as zero.  The
+ * camera block, slots with frozen != 0 and empty slots are never read and receive no gradient.
+ * Of `batch` the call reads the geometry, n_persons, seq_len, fr_start, fr_end, frozen, traj_local_pred, dheading_mask, base_orient and
+ * params (the values the poses were evaluated at); of `stage` var_mask and flags.  GLAMR_FLAG_ABSOLUTE_HEADING: GLAMR_E_UNSUPPORTED.
+ * One workgroup of 256 threads per person slot, any max_len; no atomics and a fixed summation order: two calls give the same bits.  Plain
+ * fp32: linear in the upstream gradients to rounding.  After its argument checks the call reads no host memory and does not synchronise:
+ * it can be recorded into a stream capture.  workspace: glamr_grecon_pose_backward_workspace_bytes (108 bytes per slot and frame), device
+ * memory, contents irrelevant before and after. */
+size_t glamr_grecon_pose_backward_workspace_bytes(int n_scenes, int max_persons, int max_len);
+int glamr_grecon_pose_backward(const glamr_scene_batch* batch, const glamr_stage_desc* stage,
+                               const float* g_orient_world /* (slots, max_len, 3) axis-angle, or NULL */,
+                               const float* g_trans_world /* (slots, max_len, 3), or NULL */,
+                               float* grads /* (n_scenes, scene_stride), the layout of grads_out */,
+                               int accumulate /* 1: add into grads, 0: store (everything not written = 0) */,
+                               void* workspace, void* stream);
+
 /* One torch.optim.Adam step (betas 0.9 / 0.999, eps 1e-8, no weight decay; torch/optim/adam.py _single_tensor_adam, the path
  * GlobalReconOptimizer.init_opt selects, global_recon_model.py:642) on a flat fp32 vector, with the update function the fused
  * optimiser uses: operation order of torch's CPU kernels, IEEE quotient / square root, `lr` and the bias corrections formed in double
