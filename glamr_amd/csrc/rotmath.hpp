@@ -61,7 +61,14 @@ GLAMR_HD float sqrt_(float x) { return sqrtf(x); }
 // the iteration (norms, projections, residual weights) keeps the single-instruction approximations -- measured harmless.
 //   div_:     v_rcp_f32 + the Newton / residual steps of the correctly rounded expansion (what `a / b` compiles to, minus the range
 //             scaling and the special-value fix-up: Adam's denominators are sqrt(v) / c + 1e-8 and c, normal numbers)
-//   sqrt_rn_: v_sqrt_f32 (1 ulp) corrected by the residuals of its two neighbours; exact for 0 and every normal argument
+//   sqrt_rn_: v_sqrt_f32 (1 ulp) corrected by the residuals of its two neighbours; correctly rounded for 0 and every x >= 2^-102 (3.9e-31),
+//             where a non-zero residual (a multiple of ulp(s)^2 / 2 >= 2^-149) cannot underflow.  Below that the residuals are rounded to
+//             the denormal grid, a small one becomes 0 and takes the wrong side of the comparison: the result stays within 1 ulp (MI355X:
+//             1886 of 1e6 log-uniform normal arguments off by one, all below 1.8e-34; tests/test_rotmath_gpu.py).  The caller is
+//             grecon_algo.hpp adam(): a root under 2^-51 is less than half an ulp of the 1e-8 it is added to; after the division by
+//             sqrt(1 - beta2^t) >= 0.03 its last bit reaches the denominator only where the sum straddles a rounding boundary of 1e-8's
+//             binade (gradients below 1e-14; odds under 2^-19 per update)
+//   div_:     checked bit for bit against IEEE division on the MI355X for |n|, |d| in [2^-40, 2^40] and n = 0 (the same test)
 // The host runtime uses the C operators (IEEE by definition; built with -ffp-contract=off).
 #if defined(__HIP_DEVICE_COMPILE__)
 GLAMR_HD float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
