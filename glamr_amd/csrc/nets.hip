@@ -223,13 +223,43 @@ __global__ void window_scatter_kernel(const float* y, int ldy, const int* lens, 
   if (t < lens[b] && s < lens[b] - PAST)
     for (int c = threadIdx.x; c < 69; c += blockDim.x) pose[((size_t)b * Tpad + t) * XLD + c] = y[((size_t)b * CUR + i) * ldy + c];
 }
-__global__ void pose_in_kernel(const float* body_pose, int max_len, int Tpad, float* pose) {   // [B][max_len][69] -> [B][Tpad][96]
-  const int b = blockIdx.x, t = blockIdx.y;
-  for (int c = threadIdx.x; c < XLD; c += blockDim.x) pose[((size_t)b * Tpad + t) * XLD + c] = (t < max_len && c < 69) ? body_pose[((size_t)b * max_len + t) * 69 + c] : 0.0f;
+// The two staging copies between the caller's [B][max_len][69] rows and the padded [B][Tpad][96] pose buffer: an item is one 16-byte quad of
+// a padded row, a thread walks its sequence's items with the stride of the grid's y dimension (STAGE_QUADS of them with the grids below).  As one
+// 64-thread workgroup per (sequence, frame) -- 327 680 workgroups of < 400 B each per 1024 x 300 frames -- the copies ran at a fraction of the
+// memory rate.  Same values at the same addresses.
+constexpr int STAGE_QUADS = 8;
+__global__ __launch_bounds__(64) void pose_in_kernel(const float* body_pose, int max_len, int Tpad, float* pose) {   // [B][max_len][69] -> [B][Tpad][96]
+  const int b = blockIdx.x, n = Tpad * (XLD / 4);
+  const float* src = body_pose + (size_t)b * max_len * 69;
+  float* dst = pose + (size_t)b * Tpad * XLD;
+  for (int idx = blockIdx.y * 64 + threadIdx.x; idx < n; idx += gridDim.y * 64) {
+    const int t = idx / (XLD / 4), c = 4 * (idx % (XLD / 4));
+    f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (t < max_len) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) if (c + e < 69) v[e] = src[(size_t)t * 69 + c + e];
+    }
+    *reinterpret_cast<f32x4*>(dst + (size_t)idx * 4) = v;
+  }
 }
-__global__ void pose_out_kernel(const float* pose, int max_len, int Tpad, const int* lens, float* out_pose) {
-  const int b = blockIdx.x, t = blockIdx.y;
-  for (int c = threadIdx.x; c < 69; c += blockDim.x) out_pose[((size_t)b * max_len + t) * 69 + c] = (t < lens[b]) ? pose[((size_t)b * Tpad + t) * XLD + c] : 0.0f;
+__global__ __launch_bounds__(64) void pose_out_kernel(const float* pose, int max_len, int Tpad, const int* lens, float* out_pose) {
+  const int b = blockIdx.x, n = max_len * 18, len = lens[b];      // 18 quads hold the 69 columns
+  const float* src = pose + (size_t)b * Tpad * XLD;
+  float* dst = out_pose + (size_t)b * max_len * 69;
+  for (int idx = blockIdx.y * 64 + threadIdx.x; idx < n; idx += gridDim.y * 64) {
+    const int t = idx / 18, c = 4 * (idx % 18);
+    f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (t < len) v = *reinterpret_cast<const f32x4*>(src + (size_t)t * XLD + c);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) if (c + e < 69) dst[(size_t)t * 69 + c + e] = v[e];
+  }
+}
+inline dim3 stage_grid(int B, int quads_per_seq) { return dim3(B, std::min(65535, std::max(1, (quads_per_seq + 64 * STAGE_QUADS - 1) / (64 * STAGE_QUADS)))); }
+inline void launch_pose_in(hipStream_t st, int B, const float* body_pose, int max_len, int Tpad, float* pose) {
+  hipLaunchKernelGGL(pose_in_kernel, stage_grid(B, Tpad * (XLD / 4)), dim3(64), 0, st, body_pose, max_len, Tpad, pose);
+}
+inline void launch_pose_out(hipStream_t st, int B, const float* pose, int max_len, int Tpad, const int* lens, float* out_pose) {
+  hipLaunchKernelGGL(pose_out_kernel, stage_grid(B, max_len * 18), dim3(64), 0, st, pose, max_len, Tpad, lens, out_pose);
 }
 // forward kinematics of the 23 body joints relative to the root, zero root orientation, unshaped template
 // (TrajPredVAE.get_joint_pos :384-394 -> SMPL.get_joints smpl.py:318-343); a thread per (frame, joint), the chain one tree level at a
@@ -524,7 +554,7 @@ void launch_attention(const Plan& p, int B, const float* Q, int ldq, const float
 }
 
 int ln(const Plan& p, const float* X, const float* R, const LN& n, float* Y, int rows) {      // Y = LayerNorm(X (+ R)); Y may be X or R
-  if (p.free) { hipLaunchKernelGGL(ln_free_kernel, dim3((rows + 31) / 32), dim3(64), 0, p.st, X, R, n.g, n.b, Y, rows); return GLAMR_OK; }
+  if (p.free) { hipLaunchKernelGGL(ln_free_kernel, dim3((rows + 15) / 16), dim3(64), 0, p.st, X, R, n.g, n.b, Y, rows); return GLAMR_OK; }
   hipLaunchKernelGGL(add_layernorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, p.st, X, R, n.g, n.b, Y, rows, D);
   return GLAMR_OK;
 }
@@ -581,7 +611,7 @@ int lin(const Plan& p, const Lin& L, const float* X, int ldx, float* Y, int ldy,
 int proj_ln(const Plan& p, const Lin& L, const LN& n, const float* X, const float* R, float* Y, float* tmp, int M) {
   if (!p.free && !p.keep && M >= SMALL_ROWS && L.N == D && L.K == D && L.Ws)
     return launch_rows(p.st, X, D, M, D, nullptr, 0, nullptr, nullptr, 1, 0, L.Ws, (size_t)D * L.K, L.K, L.b, ACT_NONE, R, D, n.g, n.b, Y, D);
-  if (p.free) {      // the residual in the GEMM's epilogue (same sum, same order): the three-pass LayerNorm then streams ONE array
+  if (p.free) {      // the residual in the GEMM's epilogue (same sum, same order): the LayerNorm then reads ONE array
     RC(lin(p, L, X, D, tmp, D, M, ACT_NONE, {.R = R, .ldr = D}));
     return ln(p, tmp, nullptr, n, Y, M);
   }
@@ -919,6 +949,11 @@ __global__ void dist_out_kernel(const float* pz, float* out) {
 }
 __global__ void mode_infiller_kernel(const float* pz, float* z) { z[(size_t)blockIdx.x * NZ + threadIdx.x] = pz[((size_t)blockIdx.x * 2) * D + threadIdx.x]; }
 __global__ void mode_traj_kernel(const float* pz, float* z) { z[(size_t)blockIdx.x * NZ + threadIdx.x] = pz[(size_t)blockIdx.x * D + threadIdx.x]; }
+// out[r][:] = x[r][:] for a fragment-major x of 256 columns (what a free plan leaves where a caller expects row-major rows)
+__global__ void rows_from_x32_kernel(const float* x, float* out) {
+  const int r = blockIdx.x;
+  for (int c = threadIdx.x; c < D; c += blockDim.x) out[(size_t)r * D + c] = x[x32_off(r, c, D)];
+}
 __global__ void rows_out_kernel(const float* y, int ldy, int rows, int cols, float* out) {            // out[r][c] = y[r][c], c < cols
   const int r = blockIdx.x, c = threadIdx.x;
   if (r < rows && c < cols) out[(size_t)r * cols + c] = y[(size_t)r * ldy + c];
@@ -1255,7 +1290,7 @@ int enqueue_infer(glamr_nets* h, const Plan& p, Ws& w, int B, int max_len, int n
                   float* out_orient) {
   hipStream_t st = p.st;
   const WinTape win = window_slots(w);
-  hipLaunchKernelGGL(pose_in_kernel, dim3(B, w.Tpad), dim3(64), 0, st, body_pose, max_len, w.Tpad, w.pose);
+  launch_pose_in(st, B, body_pose, max_len, w.Tpad, w.pose);
   // ---- motion infiller: autoregressive windows [30 i, 30 i + 50) ------------------------------------------------------------
   for (int i = 0; do_infill && i < n_win; ++i) {
     const int s = i * CUR;
@@ -1263,7 +1298,7 @@ int enqueue_infer(glamr_nets* h, const Plan& p, Ws& w, int B, int max_len, int n
     RC(infiller_window(h, p, win, B, GLAMR_VAE_INFER, motion_eps + (size_t)i * NZ, n_win_max * NZ, nullptr, nullptr));
     hipLaunchKernelGGL(window_scatter_kernel, dim3(B, CUR), dim3(64), 0, st, w.y, 128, w.lens, w.Tpad, s, w.pose);
   }
-  if (out_pose) hipLaunchKernelGGL(pose_out_kernel, dim3(B, max_len), dim3(64), 0, st, w.pose, max_len, w.Tpad, w.lens, out_pose);
+  if (out_pose) launch_pose_out(st, B, w.pose, max_len, w.Tpad, w.lens, out_pose);
   if (!do_traj) return GLAMR_OK;
   // ---- trajectory predictor -----------------------------------------------------------------------------------------------------
   // The WHOLE predictor runs on the LDS kernels (round 5), also what precedes its first recurrence (forward kinematics, input MLP, first input
@@ -1361,13 +1396,16 @@ extern "C" int glamr_nets_infiller_window(glamr_nets* h, int B, int mode, const 
   GLAMR_REQUIRE(mode == GLAMR_VAE_INFER || io->body_pose, "the posterior encoder (train / recon) needs body_pose");
   GLAMR_REQUIRE(mode == GLAMR_VAE_RECON || io->eps, "sampling (infer / train) needs eps");
   hipStream_t st = static_cast<hipStream_t>(stream_);
-  const Plan plan{st, h->fp32_only, false, false};
+  // GLAMR_NETS_FREE=1 (environment; a flag of the call in glamr_nets_infer) puts an INFER window on the co-schedulable kernels at ANY number of
+  // sequences: how their partial row blocks are reached with few rows (tests/test_ln_free_gpu.py)
+  const Plan plan{st, h->fp32_only, !h->fp32_only && mode == GLAMR_VAE_INFER && free_wanted(0), false};
   Ws w = ws_layout(B, WIN, static_cast<char*>(workspace));
   const WinTape win = window_slots(w);
   hipLaunchKernelGGL(window_in_kernel, dim3(B, WIN), dim3(XLD), 0, st, io->in_body_pose, io->frame_mask, w.x, w.mask);
   if (mode != GLAMR_VAE_INFER) hipLaunchKernelGGL(window_in_kernel, dim3(B, WIN), dim3(XLD), 0, st, io->body_pose, io->frame_mask, w.gx, (unsigned char*)nullptr);
   RC(infiller_window(h, plan, win, B, mode, io->eps, NZ, io->q_z, io->p_z));
-  if (io->context) GLAMR_HIP_CHECK(hipMemcpyAsync(io->context, win.enc[1].out, (size_t)B * WIN * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if (io->context && plan.free) hipLaunchKernelGGL(rows_from_x32_kernel, dim3(B * WIN), dim3(64), 0, st, win.enc[1].out, io->context);
+  else if (io->context) GLAMR_HIP_CHECK(hipMemcpyAsync(io->context, win.enc[1].out, (size_t)B * WIN * D * sizeof(float), hipMemcpyDeviceToDevice, st));
   if (io->z) GLAMR_HIP_CHECK(hipMemcpyAsync(io->z, w.z, (size_t)B * NZ * sizeof(float), hipMemcpyDeviceToDevice, st));
   hipLaunchKernelGGL(rows_out_kernel, dim3(B * CUR), dim3(128), 0, st, w.y, 128, B * CUR, 69, io->out_body_pose);
   GLAMR_HIP_CHECK(hipGetLastError());
@@ -1391,7 +1429,7 @@ extern "C" int glamr_nets_traj_clip(glamr_nets* h, int B, int T, int mode, const
   if (io->in_joint_pos) {
     hipLaunchKernelGGL(joints_in_kernel, dim3(B, T), dim3(XLD), 0, st, io->in_joint_pos, T, w.lens2, w.tx);
   } else {
-    hipLaunchKernelGGL(pose_in_kernel, dim3(B, w.Tpad), dim3(64), 0, st, io->in_body_pose, T, w.Tpad, w.pose);
+    launch_pose_in(st, B, io->in_body_pose, T, w.Tpad, w.pose);
     hipLaunchKernelGGL(fk_joints_kernel, dim3(B, (T + FK_FRAMES - 1) / FK_FRAMES), dim3(256), 0, st, w.pose, w.Tpad, T, w.lens2, h->rest_joints, h->parents, w.tx);
   }
   const float* init = nullptr;
@@ -1450,7 +1488,7 @@ extern "C" int glamr_nets_infill_taped(glamr_nets* h, int B, int max_len, const 
   Tape t = tape_layout(B, max_len, static_cast<char*>(tape_));
   bool capturing = false;
   RC(stage_lens(h, st, lens_host, B, t.lens, false, &capturing));
-  hipLaunchKernelGGL(pose_in_kernel, dim3(B, t.Tpad), dim3(64), 0, st, body_pose, max_len, t.Tpad, t.pose);
+  launch_pose_in(st, B, body_pose, max_len, t.Tpad, t.pose);
   for (int i = 0; i < n_win; ++i) {
     const WinTape& w = t.win[i];
     const int s = i * CUR;
@@ -1458,7 +1496,7 @@ extern "C" int glamr_nets_infill_taped(glamr_nets* h, int B, int max_len, const 
     RC(infiller_window(h, plan, w, B, GLAMR_VAE_INFER, motion_eps + (size_t)i * NZ, n_win_max * NZ, nullptr, nullptr));
     hipLaunchKernelGGL(window_scatter_kernel, dim3(B, CUR), dim3(64), 0, st, w.y, 128, t.lens, t.Tpad, s, t.pose);
   }
-  hipLaunchKernelGGL(pose_out_kernel, dim3(B, max_len), dim3(64), 0, st, t.pose, max_len, t.Tpad, t.lens, out_pose);
+  launch_pose_out(st, B, t.pose, max_len, t.Tpad, t.lens, out_pose);
   GLAMR_HIP_CHECK(hipGetLastError());
   return GLAMR_OK;
 }
@@ -1519,7 +1557,7 @@ extern "C" int glamr_nets_traj_taped(glamr_nets* h, int B, int max_len, const in
   if (in_joint_pos) {
     hipLaunchKernelGGL(joints_in_kernel, dim3(B, max_len), dim3(XLD), 0, st, in_joint_pos, max_len, t.lens, t.s.x);
   } else {
-    hipLaunchKernelGGL(pose_in_kernel, dim3(B, max_len), dim3(64), 0, st, in_body_pose, max_len, max_len, t.pose);
+    launch_pose_in(st, B, in_body_pose, max_len, max_len, t.pose);
     hipLaunchKernelGGL(fk_joints_kernel, dim3(B, (max_len + FK_FRAMES - 1) / FK_FRAMES), dim3(256), 0, st, t.pose, max_len, max_len, t.lens, h->rest_joints, h->parents, t.s.x);
   }
   Ws none{};                                              // (the posterior's buffers: inference mode does not touch them)

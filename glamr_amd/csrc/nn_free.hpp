@@ -239,45 +239,78 @@ inline int launch_gemm_free_bwd(hipStream_t st, const GemmArgs& a) {
   return launch_gemm_free_t<2, 1, 4, true>(st, a);
 }
 
-// Y[row] = LayerNorm(X[row] (+ R[row])) over 256 columns (add_layernorm_kernel's two-pass arithmetic), all three fragment-major; one wave per
-// 32-row block, lane (row, half) owns 128 of its row's values -- three streaming passes over the 32 KB block instead of 128 registers
+// the value of lane ^ 16 through v_permlane16_swap_b32 (the odd 16-lane rows of one operand against the even rows of the other): like
+// lane_xor32 a register-file exchange, no trip through the LDS pipeline
+__device__ __forceinline__ float lane_xor16(float x) {
+  const unsigned u = __float_as_uint(x);
+  const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+  return __uint_as_float((threadIdx.x & 16) ? r[0] : r[1]);
+}
+
+// Y[row] = LayerNorm(X[row] (+ R[row])) over 256 columns (add_layernorm_kernel's two-pass arithmetic), all three fragment-major.  One wave per
+// HALF of a 32-row block (workgroup 2 b + h: rows 32 b + 16 h ...), every value read ONCE and held in registers: lane l owns row l & 15 of the
+// half, column half (l >> 4) & 1 of the steps of parity l >> 5 -- 8 of the block's sixteen 2 KB column steps x 8 floats = 64 registers, each group
+// of 16 lanes reading 512 contiguous bytes per step.  (Until this form the kernel made three streaming passes over a whole 32-row block, lane
+// (row, column half) adding up the terms of its 16 steps in step order and then the other half's sum, to stay under the 128 registers
+// co-residency allows.)  The SUMS are those of that kernel, bit for bit -- the optimiser behind the priors amplifies a changed last bit into
+// different results: a lane forms the 8-float term of each of its 8 steps, takes the other parity's 8 terms through lane_xor32 and adds all 16 in
+// step order; the other column half's sum comes through lane_xor16 (one commutative addition: the four lanes of a row hold the same bits).  Y
+// may be X or R: a wave has read all it owns before its first store.
 __global__ __launch_bounds__(64, 4) void ln_free_kernel(const float* X, const float* R, const float* gamma, const float* beta, float* Y, int rows) {
-  const int lane = threadIdx.x, kg = lane >> 5;
-  const size_t base = ((size_t)blockIdx.x * 16 * 64 + lane) * 8;
-  auto load = [&](int s, f32x4& u, f32x4& w) {
-    u = *reinterpret_cast<const f32x4*>(X + base + (size_t)s * 512);
-    w = *reinterpret_cast<const f32x4*>(X + base + (size_t)s * 512 + 4);
-    if (R) { u += *reinterpret_cast<const f32x4*>(R + base + (size_t)s * 512); w += *reinterpret_cast<const f32x4*>(R + base + (size_t)s * 512 + 4); }
+  const int lane = threadIdx.x, half = (lane >> 4) & 1, par = lane >> 5;
+  const int row = (int)blockIdx.x * 16 + (lane & 15);
+  // step 2 i + par of the block: 1024 floats per i
+  const size_t base = (((size_t)(blockIdx.x >> 1) * 16 + par) * 64 + (row & 31) + 32 * half) * 8;
+  f32x4 v[8][2];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    v[i][0] = *reinterpret_cast<const f32x4*>(X + base + (size_t)i * 1024);
+    v[i][1] = *reinterpret_cast<const f32x4*>(X + base + (size_t)i * 1024 + 4);
+  }
+  if (R) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      v[i][0] += *reinterpret_cast<const f32x4*>(R + base + (size_t)i * 1024);
+      v[i][1] += *reinterpret_cast<const f32x4*>(R + base + (size_t)i * 1024 + 4);
+    }
+  }
+  // t[i]: this lane's term of step 2 i + par; returns the terms of steps 0 .. 15 added in that order
+  auto in_step_order = [&](const float (&t)[8]) {
+    float acc = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const float o = lane_xor32(t[i]);
+      acc += par ? o : t[i];
+      acc += par ? t[i] : o;
+    }
+    return acc;
   };
-  float sum = 0.f;
-#pragma unroll 4
-  for (int s = 0; s < 16; ++s) {
-    f32x4 u, w;
-    load(s, u, w);
-    sum += ((u[0] + u[1]) + (u[2] + u[3])) + ((w[0] + w[1]) + (w[2] + w[3]));
+  float t[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const f32x4 u = v[i][0], w = v[i][1];
+    t[i] = ((u[0] + u[1]) + (u[2] + u[3])) + ((w[0] + w[1]) + (w[2] + w[3]));
   }
-  sum += lane_xor32(sum);
+  float sum = in_step_order(t);
+  sum += lane_xor16(sum);
   const float mean = sum * (1.0f / 256.0f);
-  float sq = 0.f;
-#pragma unroll 4
-  for (int s = 0; s < 16; ++s) {
-    f32x4 u, w;
-    load(s, u, w);
-    u -= mean; w -= mean;
-    sq += ((u[0] * u[0] + u[1] * u[1]) + (u[2] * u[2] + u[3] * u[3])) + ((w[0] * w[0] + w[1] * w[1]) + (w[2] * w[2] + w[3] * w[3]));
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    v[i][0] -= mean; v[i][1] -= mean;
+    const f32x4 u = v[i][0], w = v[i][1];
+    t[i] = ((u[0] * u[0] + u[1] * u[1]) + (u[2] * u[2] + u[3] * u[3])) + ((w[0] * w[0] + w[1] * w[1]) + (w[2] * w[2] + w[3] * w[3]));
   }
-  sq += lane_xor32(sq);
+  float sq = in_step_order(t);
+  sq += lane_xor16(sq);
   const float rstd = 1.0f / sqrtf(sq * (1.0f / 256.0f) + 1e-5f);
-  if ((int)blockIdx.x * 32 + (lane & 31) >= rows) return;
-#pragma unroll 4
-  for (int s = 0; s < 16; ++s) {
-    f32x4 u, w;
-    load(s, u, w);
-    const int col = 16 * s + 8 * kg;
-    u = (u - mean) * rstd * *reinterpret_cast<const f32x4*>(gamma + col) + *reinterpret_cast<const f32x4*>(beta + col);
-    w = (w - mean) * rstd * *reinterpret_cast<const f32x4*>(gamma + col + 4) + *reinterpret_cast<const f32x4*>(beta + col + 4);
-    *reinterpret_cast<f32x4*>(Y + base + (size_t)s * 512) = u;
-    *reinterpret_cast<f32x4*>(Y + base + (size_t)s * 512 + 4) = w;
+  if (row >= rows) return;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int col = 16 * (2 * i + par) + 8 * half;
+    const f32x4 u = v[i][0] * rstd * *reinterpret_cast<const f32x4*>(gamma + col) + *reinterpret_cast<const f32x4*>(beta + col);
+    const f32x4 w = v[i][1] * rstd * *reinterpret_cast<const f32x4*>(gamma + col + 4) + *reinterpret_cast<const f32x4*>(beta + col + 4);
+    *reinterpret_cast<f32x4*>(Y + base + (size_t)i * 1024) = u;
+    *reinterpret_cast<f32x4*>(Y + base + (size_t)i * 1024 + 4) = w;
   }
 }
 

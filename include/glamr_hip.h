@@ -202,7 +202,8 @@ typedef struct glamr_infiller_io {       /* one 50-frame window per sequence; al
   float* z;                              /* out (n_seq, 128) the latent the decoder used, or NULL */
   float* out_body_pose;                  /* out (n_seq, 30, 69) the generated current frames [10, 40) */
 } glamr_infiller_io;
-/* workspace: glamr_nets_workspace_bytes(h, n_seq, 50) */
+/* workspace: glamr_nets_workspace_bytes(h, n_seq, 50).  GLAMR_NETS_FREE=1 (environment) runs a GLAMR_VAE_INFER window on the co-schedulable
+ * kernels of GLAMR_NETS_COSCHEDULE whatever n_seq is (a development aid: same outputs up to LayerNorm's summation order). */
 int glamr_nets_infiller_window(glamr_nets* h, int n_seq, int mode, const glamr_infiller_io* io, void* workspace, void* stream);
 
 typedef struct glamr_traj_io {           /* one clip of T frames per sequence; all dev fp32 */
