@@ -105,6 +105,8 @@ _SIGNATURES = {
     'glamr_grecon_last_launch_ns': (c_int, [c_void_p, POINTER(ctypes.c_double)]),
     'glamr_grecon_pose_backward_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'glamr_grecon_pose_backward': (c_int, [POINTER(SceneBatch), POINTER(StageDesc), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'glamr_grecon_cam_backward_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'glamr_grecon_cam_backward': (c_int, [POINTER(SceneBatch), POINTER(StageDesc), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'glamr_adam_step': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_int, c_void_p]),
     'glamr_adam_coef_table': (c_int, [c_double, c_int, c_void_p]),
     'glamr_adam_step_indexed': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -1,11 +1,12 @@
-"""Caller-defined loss terms on the world poses (GlobalReconOptimizer.extra_loss): the staged optimisation launch by launch
+"""Caller-defined loss terms on the world poses and the camera (GlobalReconOptimizer.extra_loss): the staged optimisation launch by launch
 on the stepwise core, with a term the caller writes in torch added to every stage's total the way a non-monitor term of loss_cfg is
 (global_recon_model.py:533-545) -- what three lines in the reference's loss_func_dict do.
 
 Per iteration of a stage: (1) the gradient launch (glamr_grecon_run_stage, one iteration with lr 0 and grads_out) gives the built-in terms'
 gradient and reports the world poses at the parameters it was taken at; (2) the callback runs under torch autograd on copies of those poses;
-(3) loss.sum().backward(); (4) glamr_grecon_pose_backward adds the term's gradient, taken from the poses back to the trajectory variables,
-to the launch's gradient array; (5) one Adam step (torch.optim.Adam's arithmetic, fresh moments per stage).  Plain launches throughout: the
+(3) loss.sum().backward(); (4) glamr_grecon_cam_backward adds the gradient with respect to ctx.cam_pose to the camera variables of the launch's
+gradient array -- or, when the camera is derived from the persons, to the residuals and to the pose gradients -- and glamr_grecon_pose_backward
+then takes the pose gradients back to the trajectory variables; (5) one Adam step (torch.optim.Adam's arithmetic, fresh moments per stage).  Plain launches throughout: the
 callback is user Python, so nothing here is captured into a graph."""
 import ctypes
 
@@ -39,13 +40,39 @@ class ExtraLossContext:
     launch reported (axis-angle / metres, by video frame; zero on frames and slots that do not exist).  exist / vis (S, P, T) bool.
     smpl_pose (S, P, T, 69), smpl_beta (S, P, T, 10): the body pose and shape of every frame (constants), or None when the batch was not
     initialised on the device.  joints() (S, P, T, 26, 3) and vertices() (S, P, T, V, 3): the body model at the world poses, differentiable
-    with respect to them (glamr_smpl_backward_root), computed when called."""
+    with respect to them (glamr_smpl_backward_root), computed when called.
+    cam_pose (S, T, 3, 4): world-to-camera, a copy of what the gradient launch reported; a leaf that requires grad when the stage optimises the
+    camera or derives it from the persons (with a fixed camera every frame holds row 0's), a plain tensor when the camera is a constant of the
+    stage.  cam_K (S, P, T, 3, 3), kp_2d (S, P, T, 26, 2), kp_score (S, P, T, 26): constants.  project(points): (S, P, T, N, 3) world points
+    -> (S, P, T, N, 2) pixels, the reference's perspective_projection(transform_trans(cam_pose, x), cam_K), differentiable with respect to the
+    points and cam_pose: project(joints()) is the reference's kp_2d_pred."""
 
-    def __init__(self, smpl, stage, iteration, seq_names, orient_world, trans_world, exist, vis, smpl_pose, smpl_beta):
+    def __init__(self, smpl, stage, iteration, seq_names, orient_world, trans_world, exist, vis, smpl_pose, smpl_beta, cam_pose=None, cam_K=None,
+                 kp_2d=None, kp_score=None):
         self._smpl = smpl
         self.stage, self.iteration, self.seq_names = stage, iteration, seq_names
         self.orient_world, self.trans_world, self.exist, self.vis = orient_world, trans_world, exist, vis
         self.smpl_pose, self.smpl_beta = smpl_pose, smpl_beta
+        self._cam, self._cam_live = cam_pose, False      # (copied at the first access: a term on the poses alone does not pay for it)
+        self.cam_K, self.kp_2d, self.kp_score = cam_K, kp_2d, kp_score
+
+    @property
+    def cam_pose(self):
+        if not self._cam_live and self._cam is not None:
+            src, grad = self._cam if isinstance(self._cam, tuple) else (self._cam, None)
+            self._cam = src if grad is None else src.clone().requires_grad_(grad)
+            self._cam_live = True
+        return self._cam
+
+    def cam_grad(self):
+        """The gradient the callback left on cam_pose, or None (never looked at, a constant, or unused)."""
+        return self._cam.grad if self._cam_live and self._cam is not None else None
+
+    def project(self, points):
+        cam = self.cam_pose[:, None, :, None]                                              # (S, 1, T, 1, 3, 4)
+        x = torch.matmul(cam[..., :3], points.unsqueeze(-1)).squeeze(-1) + cam[..., 3]     # transform_trans (torch_transform.py:257-262)
+        h = torch.matmul(self.cam_K.unsqueeze(3), x.unsqueeze(-1)).squeeze(-1)             # perspective_projection (geometry.py:23-25)
+        return h[..., :2] / (h[..., 2:] + 1e-8)
 
     def _body(self, verts):
         if self.smpl_pose is None:
@@ -78,6 +105,15 @@ class ExtraLossSchedule:
         _lib.check(L.glamr_grecon_pose_backward(ctypes.byref(sb), ctypes.byref(sd), _lib.ptr(g_orient), _lib.ptr(g_trans), _lib.ptr(grads), int(accumulate),
                                                 _lib.ptr(self._ws), _lib.current_stream()))
 
+    def cam_backward(self, sd, g_cam, grads, g_orient, g_trans, accumulate=1):
+        """glamr_grecon_cam_backward on the packed batch (current stream); g_orient / g_trans are added into (camera derived from the persons)."""
+        packed, L = self.packed, _lib.lib()
+        if getattr(self, '_cam_ws', None) is None:
+            self._cam_ws = torch.empty(L.glamr_grecon_cam_backward_workspace_bytes(packed.S, packed.P, packed.T), dtype=torch.uint8, device=packed.device)
+        sb = packed.struct()
+        _lib.check(L.glamr_grecon_cam_backward(ctypes.byref(sb), ctypes.byref(sd), _lib.ptr(g_cam), _lib.ptr(grads), int(accumulate), _lib.ptr(g_orient),
+                                               _lib.ptr(g_trans), _lib.ptr(self._cam_ws), _lib.current_stream()))
+
     def run(self, max_iters=None, has_wd=False):
         from .. import parallel
         opt, packed = self.opt, self.packed
@@ -98,6 +134,7 @@ class ExtraLossSchedule:
         pose = pa['smpl_pose'].view(S, P, T, 69) if pa is not None else None
         beta = pa['smpl_beta'].view(S, P, T, 10) if pa is not None else None
         seq_names = getattr(packed, 'seq_names', None) or ['seq%d' % si for si in range(S)]
+        cam_K, kp_2d, kp_score = packed.t['cam_K'].view(S, P, T, 3, 3), packed.t['kp_2d'].view(S, P, T, -1, 2), packed.t['kp_score'].view(S, P, T, -1)
         opt.extra_loss_history = {}
         for stage, spec in opt.opt_stage_specs.items():
             n = stepwise.stage_iters(spec, max_iters)
@@ -112,23 +149,33 @@ class ExtraLossSchedule:
                     continue
                 orient = packed.t['orient_world'].view(S, P, T, 3).clone().requires_grad_(True)
                 trans = packed.t['trans_world'].view(S, P, T, 3).clone().requires_grad_(True)
-                ctx = ExtraLossContext(opt.smpl, stage, it, seq_names, orient, trans, exist, vis, pose, beta)
+                cam_derived = 'cam' not in spec['opt_variables'] and bool(sd.flags & packing.FLAG_CAM_FROM_PERSON)
+                # (source, requires grad): a leaf in the three live modes, a plain tensor when the camera is a constant of the stage
+                cam = (packed.t['cam_pose'].view(S, T, 3, 4), 'cam' in spec['opt_variables'] or cam_derived)
+                ctx = ExtraLossContext(opt.smpl, stage, it, seq_names, orient, trans, exist, vis, pose, beta, cam, cam_K, kp_2d, kp_score)
                 with torch.enable_grad():
                     loss = opt.extra_loss(ctx)                                                        # 2.
                     if not torch.is_tensor(loss) or tuple(loss.shape) != (S,):
                         raise ValueError('extra_loss must return a tensor of shape (%d,): one value per scene' % S)
                     if not loss.requires_grad:
-                        raise ValueError('extra_loss returned a value that does not depend on ctx.orient_world / ctx.trans_world (no gradient): '
+                        raise ValueError('extra_loss returned a value that does not depend on ctx.orient_world / ctx.trans_world / ctx.cam_pose (no gradient): '
                                          'a term without a gradient would be a silent zero')
                     loss.sum().backward()                                                             # 3.
-                if orient.grad is None and trans.grad is None:
-                    raise ValueError('extra_loss returned a value that does not depend on ctx.orient_world / ctx.trans_world (grad is None)')
+                g_cam = ctx.cam_grad()
+                if orient.grad is None and trans.grad is None and g_cam is None:
+                    raise ValueError('extra_loss returned a value that does not depend on ctx.orient_world / ctx.trans_world / ctx.cam_pose (grad is None)')
                 # the stage kernel applies the world heading offset as soon as the stage optimises it (the variable exists from then on, :459-465)
                 if 'world_dheading' in spec['opt_variables']:
                     sd.flags |= packing.FLAG_HAS_WORLD_DHEADING
                 g_o = None if orient.grad is None else orient.grad.contiguous()
                 g_t = None if trans.grad is None else trans.grad.contiguous()
-                self.pose_backward(sd, g_o, g_t, grads, accumulate=1)                                 # 4.
+                if g_cam is not None:                                                                 # 4. the camera first: it may add to the pose gradients
+                    if cam_derived:
+                        g_o = torch.zeros_like(orient) if g_o is None else g_o
+                        g_t = torch.zeros_like(trans) if g_t is None else g_t
+                    self.cam_backward(sd, g_cam.contiguous(), grads, g_o if cam_derived else None, g_t if cam_derived else None, accumulate=1)
+                if g_o is not None or g_t is not None:
+                    self.pose_backward(sd, g_o, g_t, grads, accumulate=1)
                 if opt.extra_loss_grad_hook is not None:
                     opt.extra_loss_grad_hook(stage, it, grads)      # (the complete gradient of the iteration, before the update)
                 adam.step(params, m, v, grads)                                                        # 5.

@@ -429,6 +429,37 @@ int glamr_grecon_pose_backward(const glamr_scene_batch* batch, const glamr_stage
                                int accumulate /* 1: add into grads, 0: store (everything not written = 0) */,
                                void* workspace, void* stream);
 
+/* Caller-defined loss terms that see the camera: the vector-Jacobian product from the world-to-camera transforms a launch reports (cam_pose)
+ * back to what the stage optimises -- the camera block of forward (global_recon_model.py:473-508), evaluated at batch->params,
+ * orient_world, trans_world, vis and person2cam as the last launch left them.  The camera mode is read from stage->var_mask and
+ * stage->flags the way glamr_grecon_run_stage reads it:
+ *   GLAMR_VAR_CAM, not GLAMR_FLAG_FIXED_CAM: cam_pose[t] = [rot6d_to_rotmat(cam_rot6d[t]) | cam_trans[t]]; the gradient goes to cam_rot6d[t]
+ *     and cam_trans[t] of every t < seq_len.
+ *   GLAMR_VAR_CAM and GLAMR_FLAG_FIXED_CAM: every frame reads row 0; the nine gradients are the sums over t < seq_len (one block reduction,
+ *     fixed order); rows >= 1 receive nothing.
+ *   no GLAMR_VAR_CAM, GLAMR_FLAG_CAM_FROM_PERSON: with n[t] the number of persons with vis != 0 at t and src[t] the nearest frame <= t with
+ *     n > 0 (the first such frame for the frames before it), avg = sum over the persons visible at src of
+ *     [aa_to_rotmat(orient_world[src]) | trans_world[src]] . person2cam[src] / n[src]; r6 = the first two columns of avg's rotation, plus
+ *     cam_inv_rot_res[t] where n[t] == 0; cam_pose[t] = inverse([rot6d_to_rotmat(r6) | avg_t + cam_inv_trans_res[t]]).  The gradient goes to
+ *     cam_inv_trans_res[t] (every t < seq_len), cam_inv_rot_res[t] (where n[t] == 0) and, folded onto the source frames, is ADDED (whatever
+ *     `accumulate`) to g_orient_world / g_trans_world (slots, max_len, 3) of every visible person at its source frames: the buffers to hand to
+ *     glamr_grecon_pose_backward afterwards.  Both are required in this mode and ignored (may be NULL) in the other two.
+ *   neither: the camera is a constant of the stage: GLAMR_E_UNSUPPORTED, nothing is written.
+ * g_cam_pose: dev (n_scenes, max_len, 12), rows at or beyond seq_len are never read.  accumulate as in glamr_grecon_pose_backward: != 0 adds
+ * into grads and touches no other entry, 0 stores and zeroes every other entry of grads (the person blocks included).  Never read: the
+ * parameter blocks of the other camera modes and of the persons; poses and person2cam at frames where the person is not visible; empty slots
+ * and slots with frozen != 0, which count as absent and receive nothing.  One workgroup of 256 threads per scene, any max_len; no atomics and
+ * a fixed summation order: two calls give the same bits; plain fp32, linear in g_cam_pose to rounding.  After its argument checks the call
+ * reads no host memory and does not synchronise: it can be recorded into a stream capture.  workspace:
+ * glamr_grecon_cam_backward_workspace_bytes (52 bytes per scene and frame), device memory, contents irrelevant before and after. */
+size_t glamr_grecon_cam_backward_workspace_bytes(int n_scenes, int max_persons, int max_len);
+int glamr_grecon_cam_backward(const glamr_scene_batch* batch, const glamr_stage_desc* stage,
+                              const float* g_cam_pose /* (n_scenes, max_len, 12): gradient w.r.t. the reported world-to-camera 3x4 */,
+                              float* grads /* (n_scenes, scene_stride), the layout of grads_out */,
+                              int accumulate /* 1: add into grads, 0: store (everything not written = 0) */,
+                              float* g_orient_world, float* g_trans_world /* (slots, max_len, 3), added into: derived mode only */,
+                              void* workspace, void* stream);
+
 /* One torch.optim.Adam step (betas 0.9 / 0.999, eps 1e-8, no weight decay; torch/optim/adam.py _single_tensor_adam, the path
  * GlobalReconOptimizer.init_opt selects, global_recon_model.py:642) on a flat fp32 vector, with the update function the fused
  * optimiser uses: operation order of torch's CPU kernels, IEEE quotient / square root, `lr` and the bias corrections formed in double
