@@ -120,6 +120,8 @@ _SIGNATURES = {
     'glamr_rng_box_muller': (c_int, [c_int64, c_void_p, c_void_p, c_void_p]),
     'glamr_latents_draw': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'glamr_rng_set_seed': (c_int, [c_void_p, c_uint64, c_void_p]),
+    'glamr_sdf_workspace_bytes': (c_size_t, [c_int] * 5),
+    'glamr_sdf_penetration': (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_float, c_float] + [c_void_p] * 7),
 }
 
 

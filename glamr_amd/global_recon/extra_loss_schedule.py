@@ -16,23 +16,54 @@ from .. import _lib
 from . import packing, stepwise
 
 
-def check_supported(model_specs):
-    """The model flags `extra_loss` cannot be combined with; raises ValueError naming the combination."""
+def check_supported(model_specs, what='extra_loss'):
+    """The model flags `extra_loss` -- or the built-in penetration term, which runs on the same schedule -- cannot be combined with; raises
+    ValueError naming the combination."""
     g = model_specs.get
     if g('flag_opt_motion_latent', False) or g('flag_opt_traj_latent', False):
-        raise ValueError('extra_loss together with the latent-optimisation mode (flag_opt_motion_latent / flag_opt_traj_latent) is not supported: '
-                         'that mode runs a schedule of its own')
+        raise ValueError('%s together with the latent-optimisation mode (flag_opt_motion_latent / flag_opt_traj_latent) is not supported: '
+                         'that mode runs a schedule of its own' % what)
     if g('flag_opt_vis_local_rot', False):
-        raise ValueError('extra_loss together with flag_opt_vis_local_rot is not supported: the gradient mask of that flag is not applied to the term')
+        raise ValueError('%s together with flag_opt_vis_local_rot is not supported: the gradient mask of that flag is not applied to the term' % what)
     if g('absolute_heading', False):
-        raise ValueError('extra_loss together with absolute_heading is not supported: glamr_grecon_pose_backward differentiates heading increments')
+        raise ValueError('%s together with absolute_heading is not supported: glamr_grecon_pose_backward differentiates heading increments' % what)
 
 
-def check_not_sharded(packed):
+def check_not_sharded(packed, what='extra_loss'):
     """A person-sharded run (frozen person slots, or a process group of several ranks) does not exchange the term's gradient: refused."""
     import torch.distributed as dist
     if packed.t.get('frozen') is not None or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
-        raise ValueError('extra_loss together with a person-sharded run is not supported: the term would only see this rank\'s persons')
+        raise ValueError('%s together with a person-sharded run is not supported: the term would only see this rank\'s persons' % what)
+
+
+class PenetrationTerm:
+    """The built-in `penetration` term (loss_func.py:274-290) on the launch-by-launch schedule.  `vis` is constant over a run: the
+    (scene, frame) rows with at least two visible persons are found once, and every iteration skins only the visible persons of those rows
+    (SMPL with vertices, differentiable through glamr_smpl_backward_root), hands them to SDFLoss.frames and divides by the scene's length."""
+
+    def __init__(self, opt, packed, vis, pose, beta):
+        if pose is None:
+            raise RuntimeError('the penetration term needs the body pose of a batch initialised on the device (default cam_fix_frames, not a continued optimisation)')
+        S, P, T = vis.shape
+        self.smpl, self.sdf_loss, self.S = opt.smpl, opt.sdf_loss, S
+        rows = vis.sum(1) >= 2                                                            # (S, T)
+        self.s_idx, self.t_idx = rows.nonzero(as_tuple=True)                              # R rows, scene-major
+        self.active = vis[self.s_idx, :, self.t_idx].to(torch.uint8).contiguous()         # (R, P)
+        self.r_of, self.p_of = self.active.nonzero(as_tuple=True)                         # the N visible (row, person) pairs
+        s, t = self.s_idx[self.r_of], self.t_idx[self.r_of]
+        self.spt = (s, self.p_of, t)
+        self.body_pose, self.betas = pose[s, self.p_of, t].contiguous(), beta[s, self.p_of, t].contiguous()
+        self.inv_len = 1.0 / packed.t['seq_len'].view(S).to(torch.float32)                # loss_all /= max_fr (:278,289)
+
+    def __call__(self, orient, trans):
+        """orient / trans (S, P, T, 3) -> (S,) unweighted values, differentiable with respect to both."""
+        R, P = self.active.shape
+        if R == 0:
+            return torch.zeros(self.S, dtype=torch.float32, device=orient.device)
+        out = self.smpl(global_orient=orient[self.spt], body_pose=self.body_pose, betas=self.betas, root_trans=trans[self.spt], return_verts=True)
+        verts = out.vertices.new_zeros((R, P) + tuple(out.vertices.shape[1:])).index_put((self.r_of, self.p_of), out.vertices)
+        per_row = self.sdf_loss.frames(verts, self.active)
+        return torch.zeros(self.S, dtype=torch.float32, device=orient.device).index_add(0, self.s_idx, per_row) * self.inv_len
 
 
 class ExtraLossContext:
@@ -90,7 +121,8 @@ class ExtraLossContext:
 
 
 class ExtraLossSchedule:
-    """run_schedule with opt.extra_loss(ctx) -> (S,) tensor, one already weighted value per scene, added to every stage's total."""
+    """run_schedule with opt.extra_loss(ctx) -> (S,) tensor, one already weighted value per scene, added to every stage's total -- and / or the
+    built-in penetration term of the stages whose loss_cfg listed it (opt._pen_cfg: weight, monitor_only)."""
 
     def __init__(self, opt, packed, skip_term=False):
         # skip_term: the same launches and Adam steps without steps 2-4 (what a zero term must reproduce; the timing tool's baseline)
@@ -114,15 +146,33 @@ class ExtraLossSchedule:
         _lib.check(L.glamr_grecon_cam_backward(ctypes.byref(sb), ctypes.byref(sd), _lib.ptr(g_cam), _lib.ptr(grads), int(accumulate), _lib.ptr(g_orient),
                                                _lib.ptr(g_trans), _lib.ptr(self._cam_ws), _lib.current_stream()))
 
+    def _penetration_only(self, sd, spec, pen, pen_term, pen_hist, it, grads, S, P, T):
+        """Steps 2-4 for the built-in term alone: its value on copies of the reported poses, and unless it is monitor_only the weighted gradient
+        through glamr_grecon_pose_backward into `grads`.  The term does not see the camera."""
+        packed = self.packed
+        orient = packed.t['orient_world'].view(S, P, T, 3).clone().requires_grad_(not pen['monitor_only'])
+        trans = packed.t['trans_world'].view(S, P, T, 3).clone().requires_grad_(not pen['monitor_only'])
+        with torch.set_grad_enabled(not pen['monitor_only']):
+            value = pen_term(orient, trans)
+        pen_hist[:, it] = value.detach()
+        if pen['monitor_only'] or not value.requires_grad:
+            return
+        (pen['weight'] * value.sum()).backward()
+        if 'world_dheading' in spec['opt_variables']:
+            sd.flags |= packing.FLAG_HAS_WORLD_DHEADING
+        self.pose_backward(sd, orient.grad.contiguous(), trans.grad.contiguous(), grads, accumulate=1)
+
     def run(self, max_iters=None, has_wd=False):
         from .. import parallel
         opt, packed = self.opt, self.packed
-        if opt.extra_loss is None:
-            raise ValueError('ExtraLossSchedule needs GlobalReconOptimizer.extra_loss')
-        check_supported(opt.specs)
-        check_not_sharded(packed)
+        pen_cfg = getattr(opt, '_pen_cfg', None) or {}
+        if opt.extra_loss is None and not pen_cfg:
+            raise ValueError('ExtraLossSchedule needs GlobalReconOptimizer.extra_loss or a penetration term in loss_cfg')
+        what = 'extra_loss' if opt.extra_loss is not None else 'the penetration term (loss_cfg)'
+        check_supported(opt.specs, what)
+        check_not_sharded(packed, what)
         if torch.cuda.is_current_stream_capturing():
-            raise NotImplementedError('extra_loss runs launch by launch with user Python in every iteration and cannot be captured into a graph')
+            raise NotImplementedError('%s runs launch by launch with host Python in every iteration and cannot be captured into a graph' % what)
         S, P, T = packed.S, packed.P, packed.T
         params = packed.t['params']
         t_idx = torch.arange(T, device=packed.device)
@@ -136,15 +186,26 @@ class ExtraLossSchedule:
         seq_names = getattr(packed, 'seq_names', None) or ['seq%d' % si for si in range(S)]
         cam_K, kp_2d, kp_score = packed.t['cam_K'].view(S, P, T, 3, 3), packed.t['kp_2d'].view(S, P, T, -1, 2), packed.t['kp_score'].view(S, P, T, -1)
         opt.extra_loss_history = {}
+        pen_term = PenetrationTerm(opt, packed, vis, pose, beta) if pen_cfg and not self.skip_term else None
+        if pen_cfg:
+            opt.penetration_history = {}
         for stage, spec in opt.opt_stage_specs.items():
             n = stepwise.stage_iters(spec, max_iters)
             m, v = torch.zeros_like(params), torch.zeros_like(params)
             adam = stepwise.IndexedAdam(spec['opt_lr'], n, packed.device)
             hist = torch.zeros((S, n), dtype=torch.float32, device=packed.device)
+            pen = pen_cfg.get(stage)
+            pen_hist = torch.zeros((S, n), dtype=torch.float32, device=packed.device) if pen is not None else None
             for it in range(n):
                 sd = stepwise.grad_launch_desc(spec, opt.specs, has_wd, first=(it == 0))
                 grads = parallel._device_run_stage(packed, sd, True)                                  # 1.
-                if self.skip_term:
+                if self.skip_term or (opt.extra_loss is None and pen is None):      # (a stage that lists no term: the skip path)
+                    adam.step(params, m, v, grads)
+                    continue
+                if opt.extra_loss is None:
+                    self._penetration_only(sd, spec, pen, pen_term, pen_hist, it, grads, S, P, T)
+                    if opt.extra_loss_grad_hook is not None:
+                        opt.extra_loss_grad_hook(stage, it, grads)
                     adam.step(params, m, v, grads)
                     continue
                 orient = packed.t['orient_world'].view(S, P, T, 3).clone().requires_grad_(True)
@@ -160,7 +221,14 @@ class ExtraLossSchedule:
                     if not loss.requires_grad:
                         raise ValueError('extra_loss returned a value that does not depend on ctx.orient_world / ctx.trans_world / ctx.cam_pose (no gradient): '
                                          'a term without a gradient would be a silent zero')
-                    loss.sum().backward()                                                             # 3.
+                    total = loss.sum()
+                    if pen is not None:                                                               # the built-in term beside the caller's
+                        with torch.set_grad_enabled(not pen['monitor_only']):
+                            value = pen_term(orient, trans)
+                        pen_hist[:, it] = value.detach()
+                        if not pen['monitor_only']:
+                            total = total + pen['weight'] * value.sum()
+                    total.backward()                                                                  # 3.
                 g_cam = ctx.cam_grad()
                 if orient.grad is None and trans.grad is None and g_cam is None:
                     raise ValueError('extra_loss returned a value that does not depend on ctx.orient_world / ctx.trans_world / ctx.cam_pose (grad is None)')
@@ -180,7 +248,10 @@ class ExtraLossSchedule:
                     opt.extra_loss_grad_hook(stage, it, grads)      # (the complete gradient of the iteration, before the update)
                 adam.step(params, m, v, grads)                                                        # 5.
                 hist[:, it] = loss.detach()
-            opt.extra_loss_history[stage] = hist.cpu().numpy()
+            if opt.extra_loss is not None:
+                opt.extra_loss_history[stage] = hist.cpu().numpy()
+            if pen is not None:
+                opt.penetration_history[stage] = pen_hist.cpu().numpy()
             has_wd = stepwise.end_stage(packed, spec, has_wd)
         packed.has_world_dheading = has_wd
         packed.stage_ws = []

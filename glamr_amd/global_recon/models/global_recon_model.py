@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from ... import _lib
+from ...lib.models.sdf import SDFLoss
 from ...lib.models.smpl import SMPL, SMPL_MODEL_DIR
 from ...lib.utils import np_transform as nt
 from ...models import latent_rng
@@ -249,7 +250,7 @@ class GlobalReconOptimizer:
         if g('absolute_heading', False) and (g('flag_opt_motion_latent', False) or g('flag_opt_traj_latent', False)):
             raise NotImplementedError('absolute_heading together with the latent-optimisation mode')
         for flag in ('flag_opt_person2cam_rot',
-                     'flag_opt_person2cam_trans', 'flag_use_pen_loss'):
+                     'flag_opt_person2cam_trans'):
             if g(flag, False):
                 raise NotImplementedError('%s is not supported by the MI355X path' % flag)
         if g('heading_type', 'scalar') != 'scalar' or not g('flag_cam_inv_trans_res_all', True) or not g('flag_opt_cam', True):
@@ -268,6 +269,22 @@ class GlobalReconOptimizer:
         # UNWEIGHTED values, motion_latent_reg then traj_latent_reg, at the latents each iteration started from (a term the stage does not list: 0).
         packing.check_latent_regs(self.opt_stage_specs, self.specs)
         self.latent_loss_history = {}
+        # penetration (loss_func.py:274-290): the multi-person term on the skinned vertices.  Not a term of the stage kernel: its entry
+        # is taken off every stage's loss_cfg here (what every schedule and stage_desc see is the rest) and optimize / optimize_batch then run
+        # extra_loss_schedule.ExtraLossSchedule with the built-in term, added to a caller's extra_loss if one is set.  penetration_history[stage]:
+        # (scenes, iterations) UNWEIGHTED values.  Without an entry in any stage nothing changes.
+        self.flag_use_pen_loss = bool(g('flag_use_pen_loss', False))
+        packing.check_penetration(self.opt_stage_specs, self.specs)
+        self._pen_cfg = {}
+        for stage, spec in list(self.opt_stage_specs.items()):
+            rest, pen = packing.split_penetration(spec['loss_cfg'])
+            if pen is not None:
+                self._pen_cfg[stage] = pen
+                self.opt_stage_specs = dict(self.opt_stage_specs)
+                self.opt_stage_specs[stage] = dict(spec, loss_cfg=rest)
+        if self._pen_cfg:
+            extra_loss_schedule.check_supported(self.specs, what='the penetration term (loss_cfg)')
+        self.penetration_history = {}
         self.flag_filter_pose = g('flag_filter_pose', True)
         # keypoint-count filter inside filter_pose (:50-52,264-268); with HybrIK's binary scores (14 scored joints per detected frame) it is all or
         # nothing: the reference's default minimum of 15 removes every frame, 14 or less none
@@ -278,6 +295,8 @@ class GlobalReconOptimizer:
         self.cam_fix_frames = [tuple(x) for x in g('cam_fix_frames', [[0, None]])]
         self.smpl = smpl if smpl is not None else SMPL(SMPL_MODEL_DIR, pose_type='body26fk', create_transl=False).to(self.device)
         self.mt_model = mt_model if mt_model is not None else MotionTrajJointModel(None, self.device, log, smpl=self.smpl, results_root=results_root)
+        if self.flag_use_pen_loss:
+            self.sdf_loss = SDFLoss(self.smpl.faces, robustifier=True)      # (:64-65)
         self.timings = {}
 
     @property
@@ -295,9 +314,12 @@ class GlobalReconOptimizer:
     def _refuse_extra_loss(self, what):
         if self._extra_loss is not None:
             raise NotImplementedError('%s while extra_loss is set: the term runs user Python in every iteration (optimize / optimize_batch only)' % what)
+        if self._pen_cfg:
+            raise NotImplementedError('%s with the penetration term in loss_cfg: the term runs launch by launch on the skinned vertices '
+                                      '(optimize / optimize_batch only)' % what)
 
     def _run_schedule_or_extra(self, packed, max_iters, has_wd=False):
-        if self._extra_loss is None:
+        if self._extra_loss is None and not self._pen_cfg:
             return self.run_schedule(packed, max_iters, has_wd=has_wd)
         return extra_loss_schedule.ExtraLossSchedule(self, packed).run(max_iters, has_wd=has_wd)
 

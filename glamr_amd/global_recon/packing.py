@@ -46,6 +46,26 @@ def check_latent_regs(opt_stage_specs, model_specs):
                 raise ValueError('loss %r in stage %r needs %s in grecon_model_specs: the term regularises a latent that is not a parameter' % (name, stage, flag))
 
 
+PENETRATION = 'penetration'      # loss_func.py:274-290; not a term of the fused stage kernel either: extra_loss_schedule runs it
+
+
+def split_penetration(loss_cfg):
+    """loss_cfg -> (loss_cfg without the penetration term -- what stage_desc is given --, None or dict(weight, monitor_only))."""
+    c = loss_cfg.get(PENETRATION)
+    if c is None:
+        return loss_cfg, None
+    rest = {n: v for n, v in loss_cfg.items() if n != PENETRATION}
+    return rest, dict(weight=float(c['weight']), monitor_only=bool(c.get('monitor_only', False)))
+
+
+def check_penetration(opt_stage_specs, model_specs):
+    """The term reads `smpl_verts`, which the reference computes only with flag_use_pen_loss (global_recon_model.py:526-531): a KeyError
+    there, a ValueError here, before anything runs."""
+    for stage, spec in opt_stage_specs.items():
+        if PENETRATION in spec['loss_cfg'] and not model_specs.get('flag_use_pen_loss', False):
+            raise ValueError('loss %r in stage %r needs flag_use_pen_loss in grecon_model_specs: without it no vertices are computed' % (PENETRATION, stage))
+
+
 def param_layout_py(max_persons, max_len):
     """Mirror of glamr::grecon::param_layout (glamr_amd/csrc/grecon_algo.hpp); checked against the library in the tests."""
     T = max_len

@@ -624,6 +624,27 @@ int glamr_latents_draw(const uint64_t* seed_dev, const uint64_t* seq_ids, const 
                        float* teps, void* stream);
 int glamr_rng_set_seed(uint64_t* seed_dev, uint64_t seed, void* stream);
 
+/* ---- multi-person penetration (loss_func.py:274-290 `penetration`; csrc/sdf.hip, csrc/sdf.hpp) ------------------------------
+ * The reference's SDFLoss comes from the third-party `sdf` package, which is not part of it: the term is restated from the published algorithm
+ * and its definition is DESIGN.md 18 (UNPINNED against the package).  Per frame f over its active persons: bounding boxes; O_f = the persons
+ * whose box meets (closed intervals) another active person's, N_f = |O_f|; per p in O_f a grid phi_p (grid^3 voxel centres over [-1, 1]^3 of
+ * the frame (x - c_p) / s_p, c_p the box centre, s_p = (1 + scale_factor) / 2 . its longest side) holding the distance to the mesh, in
+ * normalised units, where the generalised winding number exceeds 1/2 and 0 elsewhere; then
+ *   loss[f] = 1 / N_f^2 . sum_{p in O_f} sum_{q in O_f, q != p} sum_v r(trilinear sample of phi_p at (x_{q,v} - c_p) / s_p)
+ * (zero padding, align_corners = False), r(x) = x^2 / (x^2 + rho^2), or x with rho = 0; 0 for a frame with N_f = 0.  The gradient goes to the
+ * sampled vertices only (boxes, c, s and phi are constants of it).  `faces` must be closed and oriented outwards; an index outside [0, V) is
+ * clamped.  All pointers dev, fp32 / int32 / uint8, contiguous; verts of inactive persons are never read.
+ *   g_verts (F, P, V, 3) or NULL: d loss[f] / d verts, STORED (zeros for inactive and isolated persons); NULL = forward only.
+ *   phi_out (F, P, G, G, G) [z][y][x], boxes_out (F, P, 2, 3) lo / hi, overlap_out (F, P): the intermediate results, each or NULL (zeros for
+ *     inactive persons, and in phi_out for isolated ones).
+ * Workspace: glamr_sdf_workspace_bytes, 16-byte aligned device memory, contents irrelevant before and after.  No atomics: two calls give the
+ * same bits.  After the argument checks nothing on the host is read and nothing synchronises: capturable.  grid in 2..64, 1 <= P <= 32,
+ * F . P < 2^24; otherwise GLAMR_E_INVALID (glamr_sdf_workspace_bytes: 0). */
+size_t glamr_sdf_workspace_bytes(int n_frames, int n_persons, int n_verts, int n_faces, int grid);
+int glamr_sdf_penetration(const float* verts, const unsigned char* active, const int* faces, int F, int P, int V, int NF, int grid,
+                          float scale_factor, float rho, float* loss, float* g_verts, float* phi_out, float* boxes_out, int* overlap_out,
+                          void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
