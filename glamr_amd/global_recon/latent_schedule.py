@@ -14,7 +14,7 @@ import sys
 import numpy as np
 import torch
 
-from .. import _lib, parallel
+from .. import _lib
 from ..models.priors import num_windows
 from . import packing, stepwise
 
@@ -110,7 +110,7 @@ class LatentSchedule:
         """The stage kernel's gradient launch: dL/d scene parameters (returned), dL/d j_local and -- only when the launch has a reader for it,
         the taped predictor (before opt_latent_start_iter the usual instance runs) -- dL/d traj_local_pred."""
         self.packed.t['g_traj_local'] = self.g_traj_local if with_traj_grad else None
-        return parallel._device_run_stage(self.packed, stepwise.grad_launch_desc(st.spec, self.model.specs, st.has_wd, first), True)
+        return stepwise.run_stage(self.packed, stepwise.grad_launch_desc(st.spec, self.model.specs, st.has_wd, first), True)
 
     def _backward_to_latents(self, st, pose_out, tape, ttape):
         """The gradient launch's adjoints back through the priors that ran; in a stage without a latent regulariser each latent is stepped as
@@ -239,8 +239,7 @@ class LatentSchedule:
         if model.log is None:
             return
         names = [(t, n) for t, n in enumerate(packing.LATENT_REG_TERMS) if st.regs[t][1] != _lib.LATENT_REG_ABSENT]
-        seqs = getattr(packed, 'seq_names', None) or ['seq%d' % si for si in range(packed.S)]
         for si in range(packed.S):
             for it in range(h.shape[1]):
                 loss_str = ' | '.join('%s: %7.3f' % (n, h[si, it, t]) for t, n in names)
-                model.log.info('%s - %s - %s | %4d/%d | LR: %.0e | %s' % (model.cfg_id, seqs[si], stage, it, h.shape[1], st.spec['opt_lr'], loss_str))
+                model.log.info('%s - %s - %s | %4d/%d | LR: %.0e | %s' % (model.cfg_id, packed.seq_names[si], stage, it, h.shape[1], st.spec['opt_lr'], loss_str))

@@ -271,7 +271,7 @@ class GlobalReconOptimizer:
         self.latent_loss_history = {}
         # penetration (loss_func.py:274-290): the multi-person term on the skinned vertices.  Not a term of the stage kernel: its entry
         # is taken off every stage's loss_cfg here (what every schedule and stage_desc see is the rest) and optimize / optimize_batch then run
-        # extra_loss_schedule.ExtraLossSchedule with the built-in term, added to a caller's extra_loss if one is set.  penetration_history[stage]:
+        # extra_loss_schedule.ExtraLossSchedule with the built-in term (PenetrationTerm), beside a caller's extra_loss if one is set.  penetration_history[stage]:
         # (scenes, iterations) UNWEIGHTED values.  Without an entry in any stage nothing changes.
         self.flag_use_pen_loss = bool(g('flag_use_pen_loss', False))
         packing.check_penetration(self.opt_stage_specs, self.specs)
@@ -800,9 +800,8 @@ class GlobalReconOptimizer:
             self.value_checks(rin)                                       # (first use of this batch only)
             if gate is not None and not prep_early:
                 gate.before(torch.cuda.current_stream(dev))
-        packed = packing.PackedScenes.empty(S, P, T, dev)
+        packed = packing.PackedScenes.empty(S, P, T, dev, seq_names=[str(m['seq_name']) for m in rin.meta])
         packed.person_ids = rin.ids
-        packed.seq_names = [str(m['seq_name']) for m in rin.meta]
         packed.t['cam_K'] = g['K']
         packed.t['n_persons'] = rin.n_persons
         packed.t['seq_len'] = rin.seq_len
@@ -904,7 +903,7 @@ class GlobalReconOptimizer:
             src['rel'] = packed.t['rel_transform_cam']
         ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
         host = {}
-        rin = packed.keepalive[0] if getattr(packed, 'keepalive', None) else None
+        rin = packed.keepalive[0] if packed.keepalive else None
         with ctx:
             for k, v in src.items():
                 hbuf = torch.empty(v.shape, dtype=v.dtype, pin_memory=True)      # (one pinned slab per batch was measured slower: 3 ms per allocation)
@@ -1043,12 +1042,8 @@ class GlobalReconOptimizer:
         return sd
 
     def _run(self, packed, sd):
-        import ctypes
-        L = _lib.lib()
-        sb = packed.struct()
-        ws = torch.empty(L.glamr_grecon_workspace_bytes(packed.S, packed.P, packed.T), dtype=torch.uint8, device=self.device)
-        _lib.check(L.glamr_grecon_run_stage(ctypes.byref(sb), ctypes.byref(sd), None, _lib.ptr(ws), _lib.current_stream()))
-        return ws
+        stepwise.run_stage(packed, sd, False)
+        return packed.last_ws
 
     @staticmethod
     def launch_ms(ws):
@@ -1091,9 +1086,8 @@ class GlobalReconOptimizer:
         it_secs = self.launch_ms(ws) * 1e-3 / max(1, n_it)
         hms = lambda secs: str(datetime.timedelta(seconds=round(secs)))
         names = [n for n in spec['loss_cfg'] if n in packing.LOSS_IDS]
-        seqs = getattr(packed, 'seq_names', None) or ['seq%d' % si for si in range(packed.S)]
         for si in range(packed.S):
-            head = '%s - %s - %s' % (self.cfg_id, seqs[si], stage)
+            head = '%s - %s - %s' % (self.cfg_id, packed.seq_names[si], stage)
             for it in range(n_it):
                 loss_str = ' | '.join('%s: %7.3f' % (n, h[si, it, packing.LOSS_IDS[n]]) for n in names)
                 self.log.info('%s | %4d/%d | TE: %s ETA: %s | LR: %.0e | %s' % (head, it, n_it, hms(it_secs), hms(it_secs * (n_it - it - 1)), spec['opt_lr'], loss_str))
@@ -1237,7 +1231,7 @@ class GlobalReconOptimizer:
 
     def collect(self, datas, packed, fetched=None):
         """Device arrays -> the reference's output dictionaries (numpy): one device->host copy per array.  Waits for this batch only."""
-        rin = packed.keepalive[0] if getattr(packed, 'keepalive', None) else None
+        rin = packed.keepalive[0] if packed.keepalive else None
         if datas and datas[0].get('_pending'):
             if fetched is None:
                 fetched = self._fetch_async(packed)
@@ -1251,7 +1245,7 @@ class GlobalReconOptimizer:
             all_vars = self._all_vars()
             packed.unpack_into(datas, {'opt_variables': all_vars} if self.opt_stage_specs else None, self.specs, as_torch=False)
             self.last_losses = packed.t['losses'].cpu().numpy()
-        if self.latent_mode and getattr(packed, 'latents', None) is not None and rin is not None:
+        if self.latent_mode and packed.latents is not None and rin is not None:
             # the optimised draws, per person as the reference keeps them in pose_dict (:155-158)
             meps, teps = (x.detach().cpu().numpy() for x in packed.latents)
             for si, d in enumerate(datas):
@@ -1259,7 +1253,7 @@ class GlobalReconOptimizer:
                     k = si * packed.P + pi
                     d['person_data'][idx]['motion_latent'] = meps[k, :num_windows(int(rin.lens[k]))].copy()
                     d['person_data'][idx]['traj_latent'] = teps[k][None].copy()
-        if getattr(self, 'kernel_ms', None) is not None and getattr(packed, 'stage_ws', None):
+        if getattr(self, 'kernel_ms', None) is not None and packed.stage_ws:
             self.kernel_ms.extend(self.launch_ms(ws) for ws in packed.stage_ws)
         self.timings['unpack'] = time.time() - t0
         return datas

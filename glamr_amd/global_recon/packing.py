@@ -148,13 +148,22 @@ class PackedScenes:
 
     INT_FIELDS = ('n_persons', 'seq_len', 'fr_start', 'fr_end')
 
+    def _declare(self, device, S, P, T, seq_names=None):
+        """The geometry, and what a batch carries beside its arrays -- set by whoever has it, None / [] until then: person_arrays (the per-person
+        arrays of a device initialisation), exists, keepalive ((ResidentInputs, workspace, priors' outputs)), latents ((motion, trajectory) draws),
+        stage_ws (the workspaces of the last schedule's stage launches, [] after a launch-by-launch one), last_ws (the last launch's workspace)."""
+        self.device, self.S, self.P, self.T = device, S, P, T
+        self.layout = param_layout_py(P, T)
+        self.seq_names = list(seq_names) if seq_names else ['seq%d' % si for si in range(S)]      # (the per-iteration log names its sequence)
+        self.person_arrays = self.exists = self.keepalive = self.latents = self.last_ws = None
+        self.stage_ws = []
+
     @classmethod
-    def empty(cls, n_scenes, max_persons, max_len, device, with_rel=None):
+    def empty(cls, n_scenes, max_persons, max_len, device, with_rel=None, seq_names=None):
         """All arrays allocated (zero) directly on `device`; the init kernels fill them (glamr_init_prepare / glamr_init_scenes)."""
         self = cls.__new__(cls)
         S, P, T = n_scenes, max_persons, max_len
-        self.device, self.S, self.P, self.T = device, S, P, T
-        self.layout = param_layout_py(P, T)
+        self._declare(device, S, P, T, seq_names)
         # ONE zero allocation carved into the arrays (22 allocations + 22 fill launches otherwise: host time on every batch, and on hosts
         # with slow driver calls the launches of a step are paced by it)
         spec = [('n_persons', torch.int32, (S,)), ('seq_len', torch.int32, (S,)), ('fr_start', torch.int32, (S * P,)), ('fr_end', torch.int32, (S * P,)),
@@ -176,14 +185,12 @@ class PackedScenes:
         """datas: list of `data` dicts (one per sequence); j_locals: list (per scene) of dict idx -> (T,26,3) joints computed
         with zero root orientation and zero root translation."""
         S = len(datas)
-        self.device = device
         self.person_ids = [list(d['person_data'].keys()) for d in datas]
         P = max(len(ids) for ids in self.person_ids)
         T = max(int(d['seq_len']) for d in datas)
         if P > 32:
             raise NotImplementedError('at most 32 persons per scene (csrc/grecon_wide.hip)')
-        self.S, self.P, self.T = S, P, T
-        self.layout = param_layout_py(P, T)
+        self._declare(device, S, P, T, [str(d.get('seq_name', 'seq%d' % si)) for si, d in enumerate(datas)])
         f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32)
         i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32)
         t = dict(n_persons=i32(S), seq_len=i32(S), fr_start=i32(S * P), fr_end=i32(S * P), vis=f32(S * P, T), j_local=f32(S * P, T, NJ, 3),
@@ -263,7 +270,6 @@ class PackedScenes:
                     jl_host[si * P + pi, :int(d['seq_len'])] = cpu(j_locals[si][idx]).float()
             self.t['j_local'] = jl_host.contiguous().to(device)
         self.has_world_dheading = any('world_dheading' in pd for d in datas for pd in d['person_data'].values())
-        self.seq_names = [str(d.get('seq_name', 'seq%d' % si)) for si, d in enumerate(datas)]      # (the per-iteration log names its sequence)
 
     def struct(self):
         sb = _lib.SceneBatch()

@@ -1,6 +1,9 @@
-"""What the launch-by-launch schedules share (latent_schedule.LatentSchedule, parallel.PersonShardedSchedule; stage_iters / end_stage also
-GlobalReconOptimizer.run_schedule): a stage's iteration count and epilogue, the gradient launch's descriptor, torch.optim.Adam's step with
-its step number on the device, and the capture of one iteration as a HIP graph."""
+"""What the launch-by-launch schedules share (latent_schedule.LatentSchedule, extra_loss_schedule.ExtraLossSchedule,
+parallel.PersonShardedSchedule; stage_iters / end_stage / run_stage also GlobalReconOptimizer.run_schedule): a stage's iteration count and
+epilogue, the gradient launch's descriptor, the stage launch itself (run_stage), torch.optim.Adam's step with its step number from the host
+(adam_step) or on the device (IndexedAdam), and the capture of one iteration as a HIP graph."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -28,6 +31,24 @@ def grad_launch_desc(spec, model_specs, has_wd, first, extra_flags=0):
     sd.lr = 0.0
     sd.flags |= (0 if first else packing.FLAG_KEEP_CAM_PARAMS) | extra_flags
     return sd
+
+
+def run_stage(packed, sd, want_grads, ws=None):
+    """glamr_grecon_run_stage on the packed batch (current stream); returns the gradient record (n_scenes, scene_stride) or None.  `ws`: a
+    workspace the caller keeps across launches (GLAMR_FLAG_KEEP_TABLES needs the previous launch's); a fresh one otherwise (packed.last_ws)."""
+    L = _lib.lib()
+    sb = packed.struct()
+    grads = torch.zeros_like(packed.t['params']) if want_grads else None
+    if ws is None:
+        ws = torch.empty(L.glamr_grecon_workspace_bytes(packed.S, packed.P, packed.T), dtype=torch.uint8, device=packed.device)
+    _lib.check(L.glamr_grecon_run_stage(ctypes.byref(sb), ctypes.byref(sd), _lib.ptr(grads), _lib.ptr(ws), _lib.current_stream()))
+    packed.last_ws = ws
+    return grads
+
+
+def adam_step(p, m, v, g, lr, step):
+    """glamr_adam_step: p, m, v <- one Adam step with gradient g, the 1-based step number given by the host (current stream)."""
+    _lib.check(_lib.lib().glamr_adam_step(p.numel(), _lib.ptr(p), _lib.ptr(m), _lib.ptr(v), _lib.ptr(g), float(lr), int(step), _lib.current_stream()))
 
 
 class IndexedAdam:

@@ -7,6 +7,9 @@ import os
 import torch
 import torch.distributed as dist
 
+# the device entry points of the stepwise core (PersonShardedSchedule tells them from injected ones with `is`)
+from .global_recon.stepwise import adam_step as _device_adam_step, run_stage as _device_run_stage
+
 
 def env_rank_world():
     return int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('LOCAL_RANK', '0'))
@@ -99,26 +102,6 @@ def gather_results(local_results, dst=0):
 # ------------------------------------------------------------------------------------------------------------------------------------
 # Person-sharded scenes: the collective variant of BASELINE configs[3]
 # ------------------------------------------------------------------------------------------------------------------------------------
-
-def _device_run_stage(packed, sd, want_grads, ws=None):
-    """glamr_grecon_run_stage on the packed batch (current stream); returns the gradient record (n_scenes, scene_stride) or None.  `ws`: a
-    workspace the caller keeps across launches (GLAMR_FLAG_KEEP_TABLES needs the previous launch's); a fresh one otherwise."""
-    import ctypes
-    from . import _lib
-    L = _lib.lib()
-    sb = packed.struct()
-    grads = torch.zeros_like(packed.t['params']) if want_grads else None
-    if ws is None:
-        ws = torch.empty(L.glamr_grecon_workspace_bytes(packed.S, packed.P, packed.T), dtype=torch.uint8, device=packed.device)
-    _lib.check(L.glamr_grecon_run_stage(ctypes.byref(sb), ctypes.byref(sd), _lib.ptr(grads), _lib.ptr(ws), _lib.current_stream()))
-    packed.last_ws = ws
-    return grads
-
-
-def _device_adam_step(p, m, v, g, lr, step):
-    from . import _lib
-    _lib.check(_lib.lib().glamr_adam_step(p.numel(), _lib.ptr(p), _lib.ptr(m), _lib.ptr(v), _lib.ptr(g), float(lr), int(step), _lib.current_stream()))
-
 
 class PersonShardedSchedule:
     """The staged optimisation of multi-person scenes with the PERSONS of a scene sharded over the ranks of a process group -- the variant

@@ -160,10 +160,10 @@ def _packed(asset_root):
     return data, packed
 
 
-def _run(asset_root, priors, cfg, extra=None, skip=False, iters=pe.K):
+def _run(asset_root, priors, cfg, extra=None, skip=False, iters=pe.K, make_extra=None):
     data, packed = _packed(asset_root)
     model = _model(priors, cfg)
-    model.extra_loss = extra
+    model.extra_loss = make_extra(model, packed) if make_extra is not None else extra
     first = {}
     model.extra_loss_grad_hook = lambda stage, it, g: first.setdefault(stage, g.clone()) if it == 0 else None
     xs.ExtraLossSchedule(model, packed, skip_term=skip).run(max_iters=iters)
@@ -231,6 +231,52 @@ def test_the_term_beside_a_callers_extra_loss_adds_both_gradients(asset_root, pr
     print('term + extra_loss: |both - (pen + user - none)| %.2e (bound %.2e; term %.2e, the caller term %.2e)'
           % (err, 64 * 2.0 ** -23 * scale, float((g_pen - g_none).abs().max()), float((g_user - g_none).abs().max())))
     assert err <= 64 * 2.0 ** -23 * scale
+
+
+def _without_the_term(cfg):
+    cfg = copy.deepcopy(cfg)
+    for spec in cfg['opt_stage_specs'].values():
+        spec['loss_cfg'].pop('penetration')
+    return cfg
+
+
+def _params(packed):
+    return packed.t['params'].cpu().numpy()
+
+
+def test_the_built_in_term_is_just_a_term(asset_root, priors):
+    """`penetration` in loss_cfg against the same PenetrationTerm handed in as a caller's extra_loss, times the configured weight: by the chain
+    rule both upstream gradients are exactly the weight, so every stage's first gradient and the parameters after two iterations agree bit for
+    bit, and extra_loss_history is the weight times penetration_history to the bit (one scene: the sum over scenes adds nothing)."""
+    w = pe.WEIGHT
+
+    def as_a_callers(model, packed):
+        S, P, T, pa = packed.S, packed.P, packed.T, packed.person_arrays
+        term = xs.PenetrationTerm(model, packed, packed.t['vis'].view(S, P, T) > 0, pa['smpl_pose'].view(S, P, T, 69), pa['smpl_beta'].view(S, P, T, 10))
+        return lambda ctx: w * term(ctx)
+    built_in, _, p_a, first_a = _run(asset_root, priors, pe.device_cfg(weight=w), iters=2)
+    callers, _, p_b, first_b = _run(asset_root, priors, _without_the_term(pe.device_cfg()), iters=2, make_extra=as_a_callers)
+    assert callers._pen_cfg == {} and callers.penetration_history == {} and built_in.extra_loss_history == {}
+    assert list(first_a) == list(first_b) == list(built_in.opt_stage_specs)
+    for stage in built_in.opt_stage_specs:
+        assert float(first_a[stage].abs().max()) > 0 and torch.equal(first_a[stage], first_b[stage]), stage
+        assert np.array_equal(callers.extra_loss_history[stage], np.float32(w) * built_in.penetration_history[stage]), stage
+    assert built_in.penetration_history[next(iter(first_a))][0, 0] > 0 and np.array_equal(_params(p_a), _params(p_b))
+
+
+def test_a_monitor_only_term_beside_a_callers_term_adds_nothing(asset_root, priors):
+    """monitor_only beside a caller's extra_loss: first gradients and parameters are those of the caller's term alone, bit for bit, and the
+    recorded value is the active term's."""
+    user = lambda ctx: 30.0 * ctx.trans_world[..., 0].pow(2).sum((1, 2))      # noqa: E731
+    mon, _, p_mon, first_mon = _run(asset_root, priors, pe.device_cfg(monitor_only=True), extra=user, iters=2)
+    alone, _, p_alone, first_alone = _run(asset_root, priors, _without_the_term(pe.device_cfg()), extra=user, iters=2)
+    act, _, _, _ = _run(asset_root, priors, pe.device_cfg(), iters=2)
+    assert list(first_mon) == list(first_alone) == list(mon.opt_stage_specs)
+    for stage in mon.opt_stage_specs:
+        assert torch.equal(first_mon[stage], first_alone[stage]), stage
+    assert np.abs(_params(p_mon)).max() > 0 and np.array_equal(_params(p_mon), _params(p_alone))
+    stage = list(mon.opt_stage_specs)[0]
+    assert mon.penetration_history[stage][0, 0] == act.penetration_history[stage][0, 0] > 0
 
 
 def test_refused_combinations_and_entry_points(asset_root, priors):
