@@ -30,6 +30,13 @@ class SceneBatch(Structure):
                                         'kp_2d_pred', 'orient_cam_in_world', 'frozen', 'g_j_local', 'g_traj_local', 'loss_history')]
 
 
+AUX_NUM_TERMS = 6           # GLAMR_AUX_NUM_TERMS: the terms of glamr_grecon_aux_terms (packing.AUX_LOSS_IDS names them)
+
+
+class AuxDesc(Structure):
+    _fields_ = [('loss_mask', c_uint32), ('monitor_mask', c_uint32), ('weight', c_float * AUX_NUM_TERMS), ('first_frame_weight', c_float)]
+
+
 class FilterOpts(Structure):
     _fields_ = [('filter_pose', c_int32), ('make_invis_with_keypoint', c_int32), ('keypoint_min_score', c_float), ('keypoint_min_num', c_int32)]
 
@@ -107,6 +114,8 @@ _SIGNATURES = {
     'glamr_grecon_pose_backward': (c_int, [POINTER(SceneBatch), POINTER(StageDesc), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'glamr_grecon_cam_backward_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'glamr_grecon_cam_backward': (c_int, [POINTER(SceneBatch), POINTER(StageDesc), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'glamr_grecon_aux_terms_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'glamr_grecon_aux_terms': (c_int, [POINTER(SceneBatch), POINTER(StageDesc), POINTER(AuxDesc)] + [c_void_p] * 5 + [c_int, c_void_p, c_void_p]),
     'glamr_adam_step': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_int, c_void_p]),
     'glamr_adam_coef_table': (c_int, [c_double, c_int, c_void_p]),
     'glamr_adam_step_indexed': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -1,7 +1,11 @@
-"""Loss terms the stage kernel does not hold, launch by launch on the stepwise core: the term a caller writes in torch on
-the world poses and the camera (GlobalReconOptimizer.extra_loss) and the built-in `penetration` term of loss_cfg, each added to a stage's total
-the way a non-monitor term of loss_cfg is (global_recon_model.py:533-545).  A TERM has `history` (the optimiser's attribute its values are
-published under), active(stage) and evaluate(ctx) -> ((S,) values to record, scalar contribution to the total or None: no gradient to give).
+"""Loss terms the stage kernel does not hold, launch by launch on the stepwise core: the term a caller writes in torch
+on the world poses and the camera (GlobalReconOptimizer.extra_loss), the built-in `penetration` term of loss_cfg and the six terms of
+packing.AUX_LOSS_IDS (AuxTerms, one kernel launch), each added to a stage's total the way a non-monitor term of loss_cfg is
+(global_recon_model.py:533-545).  A TERM has `history` (the optimiser's attribute its values are published under), `value_shape` (of one scene's
+record per iteration: () = a number), active(stage), evaluate(ctx) -> ((S,) + value_shape values to record, scalar contribution to the total or
+None: nothing for autograd to differentiate) and publish(stage, hist) -> what is stored under history[stage].  A term that computes its own
+adjoints (AuxTerms) adds those on variables straight into ctx.grads, the launch's gradient array, and hands the ones on trans_world / cam_pose
+to ctx.add_adjoint: they join the autograd gradients before step 4.
 
 Per iteration of a stage, one path whatever the terms: (1) the gradient launch (glamr_grecon_run_stage, one iteration with lr 0 and grads_out)
 gives the stage kernel's gradient and reports the world poses and the camera at the parameters it was taken at; (2) the stage's active terms are
@@ -39,7 +43,19 @@ def check_not_sharded(packed, what='extra_loss'):
         raise ValueError('%s together with a person-sharded run is not supported: the term would only see this rank\'s persons' % what)
 
 
-class CallerTerm:
+def aux_what(names):
+    """How a refusal names the terms of packing.AUX_LOSS_IDS a schedule was asked for."""
+    return 'the loss_cfg term%s %s' % ('' if len(names) == 1 else 's', ', '.join(sorted(names, key=packing.AUX_LOSS_IDS.get)))
+
+
+class _Term:
+    value_shape = ()
+
+    def publish(self, stage, hist):
+        return hist
+
+
+class CallerTerm(_Term):
     """opt.extra_loss(ctx) -> (S,) tensor, one already weighted value per scene: recorded as it is, added to every stage's total."""
     history = 'extra_loss_history'
 
@@ -59,7 +75,7 @@ class CallerTerm:
         return loss, loss.sum()
 
 
-class PenetrationTerm:
+class PenetrationTerm(_Term):
     """The built-in `penetration` term (loss_func.py:274-290) of the stages opt._pen_cfg lists ({stage: weight, monitor_only}).
     `vis` is constant over a run: the (scene, frame) rows with at least two visible persons are found once, and every evaluation skins only the
     visible persons of those rows (SMPL with vertices, differentiable through glamr_smpl_backward_root), hands them to SDFLoss.frames and divides
@@ -104,6 +120,56 @@ class PenetrationTerm:
             return value, (cfg['weight'] * value.sum() if value.requires_grad else None)      # (None: monitor_only, or no row to look at)
 
 
+class AuxTerms(_Term):
+    """The terms of packing.AUX_LOSS_IDS of the stages opt._aux_cfg lists ({stage: {name: weight, monitor_only[,
+    first_frame_weight]}}): ONE launch of glamr_grecon_aux_terms per iteration gives the six unweighted values and the weighted adjoints, at
+    the params, trans_world and cam_pose the gradient launch left in the batch.  Nothing goes through autograd: the adjoints of the terms that
+    live on variables (cam_rot_smoothness, cam_trans_smoothness, local_traj_dheading_reg) are added to ctx.grads by the kernel, those on
+    trans_world / cam_pose go to ctx.add_adjoint.
+    The cam_rot6d / cam_trans rows of params ARE the stage's variables when the kernel reads them: a stage's first gradient launch
+    (grad_launch_desc(first=True)) sets them from cam_pose (grecon_algo.hpp: the `var_cam && !GLAMR_FLAG_KEEP_CAM_PARAMS` block) and writes them to
+    the batch array, every later one keeps what Adam made of them; packing.check_aux has refused the two terms on these rows in a stage that
+    does not optimise `cam`.
+    root_trans_cam: person_arrays['trans_cam'] of a batch initialised on the device, the packed pd['root_trans_cam'] of host dictionaries.
+    prepare=False: for a run that never evaluates the terms (skip_term)."""
+    history = 'aux_loss_history'
+    value_shape = (_lib.AUX_NUM_TERMS,)
+    _ON_TRANS = (1 << packing.AUX_LOSS_IDS['traj_trans_smoothness']) | (1 << packing.AUX_LOSS_IDS['cam_traj_trans'])
+    _ON_CAM = (1 << packing.AUX_LOSS_IDS['cam_depth_smoothness']) | (1 << packing.AUX_LOSS_IDS['cam_traj_trans'])
+
+    def __init__(self, opt, packed, prepare=True):
+        self.cfg, self.packed = opt._aux_cfg, packed
+        if not prepare:
+            return
+        self.desc = {stage: packing.aux_desc(c) for stage, c in self.cfg.items()}
+        pa = packed.person_arrays
+        self.root_trans_cam = pa['trans_cam'] if pa is not None and pa.get('trans_cam') is not None else packed.root_trans_cam
+        if self.root_trans_cam is None and any('cam_traj_trans' in c for c in self.cfg.values()):
+            raise RuntimeError('cam_traj_trans needs root_trans_cam of every person (person_data[...][\'root_trans_cam\'])')
+        self._ws = torch.empty(max(_lib.lib().glamr_grecon_aux_terms_workspace_bytes(packed.S, packed.P, packed.T), 4), dtype=torch.uint8, device=packed.device)
+
+    def active(self, stage):
+        return stage in self.cfg
+
+    def evaluate(self, ctx):
+        packed, ad, sd = self.packed, self.desc[ctx.stage], ctx.stage_desc
+        S, P, T = packed.S, packed.P, packed.T
+        live = ad.loss_mask & ~ad.monitor_mask
+        cam_constant = not (sd.var_mask & packing.VAR_BITS['cam']) and not (sd.flags & packing.FLAG_CAM_FROM_PERSON)
+        zeros = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=packed.device)
+        g_trans = zeros(S * P, T, 3) if live & self._ON_TRANS else None
+        g_cam = zeros(S, T, 12) if live & self._ON_CAM and not cam_constant else None
+        values = torch.empty((S, _lib.AUX_NUM_TERMS), dtype=torch.float32, device=packed.device)
+        sb = packed.struct()
+        _lib.check(_lib.lib().glamr_grecon_aux_terms(ctypes.byref(sb), ctypes.byref(sd), ctypes.byref(ad), _lib.ptr(self.root_trans_cam), _lib.ptr(values),
+                                                     _lib.ptr(g_trans), _lib.ptr(g_cam), _lib.ptr(ctx.grads), 1, _lib.ptr(self._ws), _lib.current_stream()))
+        ctx.add_adjoint(trans_world=g_trans, cam_pose=g_cam)
+        return values, None
+
+    def publish(self, stage, hist):
+        return {name: hist[:, :, i] for name, i in packing.AUX_LOSS_IDS.items() if name in self.cfg[stage]}
+
+
 class ExtraLossContext:
     """What the callback is given.  orient_world / trans_world (S, P, T, 3): leaf tensors that require grad, copies of the poses the gradient
     launch reported (axis-angle / metres, by video frame; zero on frames and slots that do not exist).  exist / vis (S, P, T) bool.
@@ -114,11 +180,15 @@ class ExtraLossContext:
     camera or derives it from the persons (with a fixed camera every frame holds row 0's), a plain tensor when the camera is a constant of the
     stage.  cam_K (S, P, T, 3, 3), kp_2d (S, P, T, 26, 2), kp_score (S, P, T, 26): constants.  project(points): (S, P, T, N, 3) world points
     -> (S, P, T, N, 2) pixels, the reference's perspective_projection(transform_trans(cam_pose, x), cam_K), differentiable with respect to the
-    points and cam_pose: project(joints()) is the reference's kp_2d_pred."""
+    points and cam_pose: project(joints()) is the reference's kp_2d_pred.
+    For a term that computes its own adjoints: stage_desc (the gradient launch's descriptor), grads ((S, scene_stride), the launch's gradient
+    array: adjoints on variables are added in place) and add_adjoint(trans_world=, cam_pose=): adjoints shaped like trans_world / cam_pose (any
+    view of the same elements) that join the autograd gradients of the iteration."""
 
     def __init__(self, smpl, stage, iteration, seq_names, orient_world, trans_world, exist, vis, smpl_pose, smpl_beta, cam_pose=None, cam_K=None,
-                 kp_2d=None, kp_score=None):
+                 kp_2d=None, kp_score=None, stage_desc=None, grads=None):
         self._smpl = smpl
+        self.stage_desc, self.grads, self.adjoints = stage_desc, grads, {}
         self.stage, self.iteration, self.seq_names = stage, iteration, seq_names
         self.orient_world, self.trans_world, self.exist, self.vis = orient_world, trans_world, exist, vis
         self.smpl_pose, self.smpl_beta = smpl_pose, smpl_beta
@@ -132,6 +202,11 @@ class ExtraLossContext:
             self._cam = src if grad is None else src.clone().requires_grad_(grad)
             self._cam_live = True
         return self._cam
+
+    def add_adjoint(self, **adjoints):
+        for k, v in adjoints.items():
+            if v is not None:
+                self.adjoints[k] = v if k not in self.adjoints else self.adjoints[k] + v.view_as(self.adjoints[k])
 
     def cam_grad(self):
         """The gradient the callback left on cam_pose, or None (never looked at, a constant, or unused)."""
@@ -222,7 +297,7 @@ class ExtraLossSchedule:
         cam_derived = 'cam' not in opt_vars and bool(sd.flags & packing.FLAG_CAM_FROM_PERSON)
         # (source, requires grad): a leaf in the three live modes, a plain tensor when the camera is a constant of the stage
         cam = (packed.t['cam_pose'].view(S, T, 3, 4), 'cam' in opt_vars or cam_derived)
-        ctx = ExtraLossContext(self.opt.smpl, st.name, it, orient_world=orient, trans_world=trans, cam_pose=cam, **self.const)
+        ctx = ExtraLossContext(self.opt.smpl, st.name, it, orient_world=orient, trans_world=trans, cam_pose=cam, stage_desc=sd, grads=grads, **self.const)
         values, total = [], None
         with torch.enable_grad():
             for term, _ in st.terms:                                                                  # 2.
@@ -230,17 +305,24 @@ class ExtraLossSchedule:
                 values.append(value.detach())
                 if part is not None:
                     total = part if total is None else total + part
-            if total is None:                                   # (monitor-only terms alone, or no row for the built-in term to see)
+            if total is None and not ctx.adjoints:              # (monitor-only terms alone, or no row for the built-in term to see)
                 return values
-            total.backward()                                                                          # 3.
+            if total is not None:
+                total.backward()                                                                      # 3.
         g_cam = ctx.cam_grad()
-        if orient.grad is None and trans.grad is None and g_cam is None:
+        if total is not None and orient.grad is None and trans.grad is None and g_cam is None:
             raise ValueError('extra_loss returned a value that does not depend on ctx.orient_world / ctx.trans_world / ctx.cam_pose (grad is None)')
         # the stage kernel applies the world heading offset as soon as the stage optimises it (the variable exists from then on, :459-465)
         if 'world_dheading' in opt_vars:
             sd.flags |= packing.FLAG_HAS_WORLD_DHEADING
         g_o = None if orient.grad is None else orient.grad.contiguous()
         g_t = None if trans.grad is None else trans.grad.contiguous()
+        if 'trans_world' in ctx.adjoints:                       # (a term's own adjoints: added to autograd's)
+            a = ctx.adjoints['trans_world'].view(S, P, T, 3)
+            g_t = a if g_t is None else g_t + a
+        if 'cam_pose' in ctx.adjoints:
+            a = ctx.adjoints['cam_pose'].view(S, T, 3, 4)
+            g_cam = a if g_cam is None else g_cam + a
         if g_cam is not None:                                                                         # 4. the camera first: it may add to the pose gradients
             if cam_derived:
                 g_o = torch.zeros_like(orient) if g_o is None else g_o
@@ -252,9 +334,10 @@ class ExtraLossSchedule:
 
     def run(self, max_iters=None, has_wd=False):
         opt, packed, c = self.opt, self.packed, self.const
-        if opt.extra_loss is None and not opt._pen_cfg:
-            raise ValueError('ExtraLossSchedule needs GlobalReconOptimizer.extra_loss or a penetration term in loss_cfg')
-        what = 'extra_loss' if opt.extra_loss is not None else 'the penetration term (loss_cfg)'
+        if opt.extra_loss is None and not opt._pen_cfg and not opt._aux_cfg:
+            raise ValueError('ExtraLossSchedule needs GlobalReconOptimizer.extra_loss, a penetration term or a term of packing.AUX_LOSS_IDS in loss_cfg')
+        what = 'extra_loss' if opt.extra_loss is not None else 'the penetration term (loss_cfg)' if opt._pen_cfg else \
+            aux_what({n for c in opt._aux_cfg.values() for n in c})
         check_supported(opt.specs, what)
         check_not_sharded(packed, what)
         if torch.cuda.is_current_stream_capturing():
@@ -263,17 +346,19 @@ class ExtraLossSchedule:
         terms = [CallerTerm(opt.extra_loss)] if opt.extra_loss is not None else []
         if opt._pen_cfg:
             terms.append(PenetrationTerm(opt, packed, c['vis'], c['smpl_pose'], c['smpl_beta'], prepare=not self.skip_term))
+        if opt._aux_cfg:
+            terms.append(AuxTerms(opt, packed, prepare=not self.skip_term))
         opt.extra_loss_history = {}
         for term in terms:
             setattr(opt, term.history, {})
         for stage, spec in opt.opt_stage_specs.items():
             n = stepwise.stage_iters(spec, max_iters)
-            st = _Stage(stage, spec, has_wd, [(term, torch.zeros((packed.S, n), dtype=torch.float32, device=packed.device)) for term in terms if term.active(stage)],
+            st = _Stage(stage, spec, has_wd, [(term, torch.zeros((packed.S, n) + term.value_shape, dtype=torch.float32, device=packed.device)) for term in terms if term.active(stage)],
                         torch.zeros_like(self.params), torch.zeros_like(self.params), stepwise.IndexedAdam(spec['opt_lr'], n, packed.device))
             for it in range(n):
                 self.iteration(st, it)
             for term, hist in st.terms:
-                getattr(opt, term.history)[stage] = hist.cpu().numpy()
+                getattr(opt, term.history)[stage] = term.publish(stage, hist.cpu().numpy())
             has_wd = stepwise.end_stage(packed, spec, has_wd)
         packed.has_world_dheading = has_wd
         packed.stage_ws = []

@@ -285,6 +285,20 @@ class GlobalReconOptimizer:
         if self._pen_cfg:
             extra_loss_schedule.check_supported(self.specs, what='the penetration term (loss_cfg)')
         self.penetration_history = {}
+        # the six terms of packing.AUX_LOSS_IDS (cam_rot_smoothness ... local_traj_dheading_reg): taken off every stage's loss_cfg
+        # like the penetration term and run by the same schedule (extra_loss_schedule.AuxTerms, one launch of glamr_grecon_aux_terms per
+        # iteration).  aux_loss_history[stage][name]: (scenes, iterations) UNWEIGHTED values.  Without one of the names in any stage nothing changes.
+        packing.check_aux(self.opt_stage_specs, self.specs)
+        self._aux_cfg = {}
+        for stage, spec in list(self.opt_stage_specs.items()):
+            rest, aux = packing.split_aux(spec['loss_cfg'])
+            if aux is not None:
+                self._aux_cfg[stage] = aux
+                self.opt_stage_specs = dict(self.opt_stage_specs)
+                self.opt_stage_specs[stage] = dict(spec, loss_cfg=rest)
+        if self._aux_cfg:
+            extra_loss_schedule.check_supported(self.specs, what=extra_loss_schedule.aux_what({n for c in self._aux_cfg.values() for n in c}))
+        self.aux_loss_history = {}
         self.flag_filter_pose = g('flag_filter_pose', True)
         # keypoint-count filter inside filter_pose (:50-52,264-268); with HybrIK's binary scores (14 scored joints per detected frame) it is all or
         # nothing: the reference's default minimum of 15 removes every frame, 14 or less none
@@ -317,9 +331,12 @@ class GlobalReconOptimizer:
         if self._pen_cfg:
             raise NotImplementedError('%s with the penetration term in loss_cfg: the term runs launch by launch on the skinned vertices '
                                       '(optimize / optimize_batch only)' % what)
+        if self._aux_cfg:
+            raise NotImplementedError('%s with %s: these terms run launch by launch on a kernel of their own (optimize / optimize_batch only)'
+                                      % (what, extra_loss_schedule.aux_what({n for c in self._aux_cfg.values() for n in c})))
 
     def _run_schedule_or_extra(self, packed, max_iters, has_wd=False):
-        if self._extra_loss is None and not self._pen_cfg:
+        if self._extra_loss is None and not self._pen_cfg and not self._aux_cfg:
             return self.run_schedule(packed, max_iters, has_wd=has_wd)
         return extra_loss_schedule.ExtraLossSchedule(self, packed).run(max_iters, has_wd=has_wd)
 

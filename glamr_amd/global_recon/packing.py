@@ -66,6 +66,59 @@ def check_penetration(opt_stage_specs, model_specs):
             raise ValueError('loss %r in stage %r needs flag_use_pen_loss in grecon_model_specs: without it no vertices are computed' % (PENETRATION, stage))
 
 
+# The remaining terms of the reference's loss_func_dict that need no variable the optimiser lacks (loss_func.py:60-73, 94-103, 135-144, 175-186,
+# 216-217), in the order of glamr_grecon_aux_terms' values (GLAMR_AUX_*).  Not terms of the fused stage kernel either: extra_loss_schedule.AuxTerms
+# runs them on a kernel of their own.
+AUX_LOSS_IDS = {'cam_rot_smoothness': 0, 'cam_trans_smoothness': 1, 'cam_depth_smoothness': 2, 'traj_trans_smoothness': 3, 'cam_traj_trans': 4,
+                'local_traj_dheading_reg': 5}
+AUX_ON_CAM_VARIABLES = ('cam_rot_smoothness', 'cam_trans_smoothness')      # read data['cam_rot_6d'] / data['cam_trans']
+
+
+def split_aux(loss_cfg):
+    """loss_cfg -> (loss_cfg without the terms of AUX_LOSS_IDS, None or {name: dict(weight, monitor_only[, first_frame_weight])} in loss_cfg's order)."""
+    aux = {}
+    for name, c in loss_cfg.items():
+        if name not in AUX_LOSS_IDS:
+            continue
+        if c.get('rot_type', '6d') != '6d' or c.get('first_frame_trans_only', False):
+            raise NotImplementedError('loss option not supported: %s %s' % (name, c))
+        aux[name] = dict(weight=float(c['weight']), monitor_only=bool(c.get('monitor_only', False)))
+        if name == 'cam_traj_trans' and 'first_frame_weight' in c:
+            aux[name]['first_frame_weight'] = float(c['first_frame_weight'])
+    if not aux:
+        return loss_cfg, None
+    return {n: v for n, v in loss_cfg.items() if n not in AUX_LOSS_IDS}, aux
+
+
+def check_aux(opt_stage_specs, model_specs):
+    """cam_rot_smoothness / cam_trans_smoothness read data['cam_rot_6d'] / data['cam_trans'], which only a stage that optimises `cam` sets
+    (global_recon_model.py:473-480): a KeyError in the reference -- or, silently, the stale tensor an earlier stage left behind.  A ValueError
+    here, before anything runs."""
+    for stage, spec in opt_stage_specs.items():
+        for name in AUX_ON_CAM_VARIABLES:
+            if name in spec['loss_cfg'] and 'cam' not in spec['opt_variables']:
+                raise ValueError("loss %r in stage %r needs 'cam' in the stage's opt_variables: the term reads the camera variables themselves, which exist only "
+                                 "in a stage that optimises them (a KeyError in the reference, or the stale tensor of an earlier stage)" % (name, stage))
+
+
+def aux_desc(aux_cfg):
+    """split_aux's second result -> glamr_aux_desc."""
+    ad = _lib.AuxDesc()
+    ad.loss_mask = ad.monitor_mask = 0
+    ad.first_frame_weight = 1.0
+    for i in range(_lib.AUX_NUM_TERMS):
+        ad.weight[i] = 0.0
+    for name, c in aux_cfg.items():
+        i = AUX_LOSS_IDS[name]
+        ad.loss_mask |= 1 << i
+        ad.weight[i] = c['weight']
+        if c['monitor_only']:
+            ad.monitor_mask |= 1 << i
+        if 'first_frame_weight' in c:
+            ad.first_frame_weight = c['first_frame_weight']
+    return ad
+
+
 def param_layout_py(max_persons, max_len):
     """Mirror of glamr::grecon::param_layout (glamr_amd/csrc/grecon_algo.hpp); checked against the library in the tests."""
     T = max_len
@@ -156,6 +209,7 @@ class PackedScenes:
         self.layout = param_layout_py(P, T)
         self.seq_names = list(seq_names) if seq_names else ['seq%d' % si for si in range(S)]      # (the per-iteration log names its sequence)
         self.person_arrays = self.exists = self.keepalive = self.latents = self.last_ws = None
+        self.root_trans_cam = None      # (S * P, T, 3) the persons' pd['root_trans_cam'] of a batch packed from host dictionaries (cam_traj_trans reads it)
         self.stage_ws = []
 
     @classmethod
@@ -255,6 +309,12 @@ class PackedScenes:
             if P > 1 and d.get('rel_transform_cam'):
                 for (i, j), M in d['rel_transform_cam'].items():
                     t['rel_transform_cam'][si, i, j, :Ts] = cpu(M)[:, :3, :].reshape(Ts, 12).float()
+        if all('root_trans_cam' in pd for d in datas for pd in d['person_data'].values()):
+            rtc = f32(S * P, T, 3)
+            for si, d in enumerate(datas):
+                for pi, idx in enumerate(self.person_ids[si]):
+                    rtc[si * P + pi, :int(d['seq_len'])] = cpu(d['person_data'][idx]['root_trans_cam']).float()
+            self.root_trans_cam = rtc.to(device)
         jl_host = t.pop('j_local')
         self.t = {k: v.contiguous().to(device) for k, v in t.items()}
         first_jl = j_locals[0][self.person_ids[0][0]]

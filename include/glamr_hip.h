@@ -460,6 +460,56 @@ int glamr_grecon_cam_backward(const glamr_scene_batch* batch, const glamr_stage_
                               float* g_orient_world, float* g_trans_world /* (slots, max_len, 3), added into: derived mode only */,
                               void* workspace, void* stream);
 
+/* The loss_cfg terms of the reference the stage kernel does not hold, on a kernel of their own (csrc/grecon_aux.hpp): one
+ * launch evaluates every term of aux->loss_mask for every scene and returns the UNWEIGHTED values together with the WEIGHTED adjoints of the
+ * terms that are not in aux->monitor_mask -- their part of compute_loss (global_recon_model.py:533-545) and of `loss.backward()` (:556).
+ * Everything is evaluated at what the stage's gradient launch left in the batch: params, trans_world and cam_pose = [R_t | c_t].  With T =
+ * the scene's seq_len, persons q < n_persons, n_q = fr_end - fr_start of slot q (global_recon/models/loss_func.py):
+ *   GLAMR_AUX_CAM_ROT_SMOOTHNESS      :60-65    mean over t < T-1 of sum_6 (30 (r[t] - r[t+1]))^2 on the RAW cam_rot6d rows of params (not
+ *                                               re-normalised columns); adjoint into the cam_rot6d rows of grads
+ *   GLAMR_AUX_CAM_TRANS_SMOOTHNESS    :68-73    the same on the cam_trans rows (3 per frame); adjoint into the cam_trans rows of grads
+ *       both need GLAMR_VAR_CAM (GLAMR_E_UNSUPPORTED without: the rows are not the stage's variables, a KeyError or a stale tensor in the
+ *       reference); with GLAMR_FLAG_FIXED_CAM every row is row 0: the value is exactly 0 and nothing is written
+ *   GLAMR_AUX_CAM_DEPTH_SMOOTHNESS    :94-103   o_t = -R_t^T c_t, z_t = third row of R_t, d_t = 30 (o_t - o_{t+1}) . z_{t+1} (the LATER frame's
+ *                                               axis); SUM over t < T-1 of d_t^2 (the reference takes the mean of a scalar); adjoint into g_cam_pose
+ *   GLAMR_AUX_TRAJ_TRANS_SMOOTHNESS   :135-144  sum_q sum_{t < T-1} |30 (x_q[t+1] - x_q[t])|^2 / (n_persons (T - 1)) over ALL frames of every
+ *                                               present slot (as the fused traj_rot_smoothness); adjoint into g_trans_world
+ *   GLAMR_AUX_CAM_TRAJ_TRANS          :175-186  per person over frames with vis != 0: diff = R_t x_q[t] + c_t - root_trans_cam_q[t], the diff
+ *                                               of the person's first visible frame times aux->first_frame_weight; sum diff^2 / sum_q n_vis_q;
+ *                                               adjoints into g_trans_world and g_cam_pose
+ *   GLAMR_AUX_LOCAL_TRAJ_DHEADING_REG :216-217, 189-196  sum_q sum_{e=1..n_q-1} (30 dh_q[e])^2 / sum_q (n_q - 1) on the local_dheading variable
+ *                                               itself (dheading_mask does not enter); adjoint into the local_dheading rows of grads, only
+ *                                               when stage->var_mask has GLAMR_VAR_LOCAL_DHEADING
+ * A zero denominator (T == 1, nobody visible, every n_q == 1) is NaN in the reference; here the value is 0 and no gradient is given (a NaN
+ * would poison Adam's moments of the whole scene): the one deliberate deviation.
+ * values: dev (n_scenes, GLAMR_AUX_NUM_TERMS), every entry written (0 for a term outside loss_mask).  g_trans_world: dev (slots, max_len, 3)
+ * and g_cam_pose: dev (n_scenes, max_len, 12), the layouts glamr_grecon_pose_backward / glamr_grecon_cam_backward read; grads: dev
+ * (n_scenes, scene_stride), the layout of grads_out.  Each may be NULL when no term outside the monitor mask writes to it.  When the camera is
+ * a constant of the stage (neither GLAMR_VAR_CAM nor GLAMR_FLAG_CAM_FROM_PERSON) the camera terms give their values, nothing is added to
+ * g_cam_pose, and cam_traj_trans still gives g_trans_world.  accumulate as in glamr_grecon_cam_backward: != 0 ADDS the adjoints and touches
+ * nothing else, 0 zero-fills every given output array (all of it) first.  root_trans_cam: dev (slots, max_len, 3), read at visible frames
+ * only; required by cam_traj_trans alone.  Never read: rows at or beyond seq_len, empty slots, the parameter blocks of terms outside
+ * loss_mask, poses and root_trans_cam at frames cam_traj_trans does not look at (when traj_trans_smoothness / cam_depth_smoothness are
+ * off).  batch->frozen != NULL: GLAMR_E_UNSUPPORTED.  Of `stage` var_mask and flags are read (the camera mode as glamr_grecon_run_stage reads it).
+ * One workgroup of 256 threads per scene, any max_len; no atomics and a fixed summation order: two calls give the same bits; plain fp32.
+ * After its argument checks the call reads no host memory and does not synchronise: it can be recorded into a stream capture.  workspace:
+ * glamr_grecon_aux_terms_workspace_bytes (4 bytes per slot), device memory, contents irrelevant before and after. */
+enum { GLAMR_AUX_CAM_ROT_SMOOTHNESS = 0, GLAMR_AUX_CAM_TRANS_SMOOTHNESS = 1, GLAMR_AUX_CAM_DEPTH_SMOOTHNESS = 2,
+       GLAMR_AUX_TRAJ_TRANS_SMOOTHNESS = 3, GLAMR_AUX_CAM_TRAJ_TRANS = 4, GLAMR_AUX_LOCAL_TRAJ_DHEADING_REG = 5, GLAMR_AUX_NUM_TERMS = 6 };
+typedef struct glamr_aux_desc {
+  uint32_t loss_mask;                    /* bit GLAMR_AUX_*: the term is evaluated */
+  uint32_t monitor_mask;                 /* bit GLAMR_AUX_*: monitor_only -- the value and no gradient */
+  float weight[GLAMR_AUX_NUM_TERMS];     /* loss_cfg weight per term: scales the adjoints, never the values */
+  float first_frame_weight;              /* cam_traj_trans: factor of a person's first visible frame (reference default 1) */
+} glamr_aux_desc;
+size_t glamr_grecon_aux_terms_workspace_bytes(int n_scenes, int max_persons, int max_len);
+int glamr_grecon_aux_terms(const glamr_scene_batch* batch, const glamr_stage_desc* stage, const glamr_aux_desc* aux,
+                           const float* root_trans_cam /* (slots, max_len, 3), or NULL without cam_traj_trans */,
+                           float* values /* (n_scenes, GLAMR_AUX_NUM_TERMS) unweighted */,
+                           float* g_trans_world /* (slots, max_len, 3) */, float* g_cam_pose /* (n_scenes, max_len, 12) */,
+                           float* grads /* (n_scenes, scene_stride), the layout of grads_out */,
+                           int accumulate /* 1: add, 0: zero-fill the given outputs first */, void* workspace, void* stream);
+
 /* One torch.optim.Adam step (betas 0.9 / 0.999, eps 1e-8, no weight decay; torch/optim/adam.py _single_tensor_adam, the path
  * GlobalReconOptimizer.init_opt selects, global_recon_model.py:642) on a flat fp32 vector, with the update function the fused
  * optimiser uses: operation order of torch's CPU kernels, IEEE quotient / square root, `lr` and the bias corrections formed in double
