@@ -334,11 +334,9 @@ class ExtraLossSchedule:
 
     def run(self, max_iters=None, has_wd=False):
         opt, packed, c = self.opt, self.packed, self.const
-        if opt.extra_loss is None and not opt._pen_cfg and not opt._aux_cfg:
+        what = opt._off_kernel_term()      # (its combination with the model's flags was checked where the term was set: the optimiser's __init__ / extra_loss)
+        if what is None:
             raise ValueError('ExtraLossSchedule needs GlobalReconOptimizer.extra_loss, a penetration term or a term of packing.AUX_LOSS_IDS in loss_cfg')
-        what = 'extra_loss' if opt.extra_loss is not None else 'the penetration term (loss_cfg)' if opt._pen_cfg else \
-            aux_what({n for c in opt._aux_cfg.values() for n in c})
-        check_supported(opt.specs, what)
         check_not_sharded(packed, what)
         if torch.cuda.is_current_stream_capturing():
             raise NotImplementedError('%s runs launch by launch with host Python in every iteration and cannot be captured into a graph' % what)

@@ -164,7 +164,7 @@ class LatentSchedule:
     def _record_trace(self, st, g, with_priors):
         """model.latent_trace (a dict the parity tests set): the two values of the run's first regularised iteration, and the state and the
         latent gradients of the first iteration of the run in which a gradient came back through the priors."""
-        trace, t = getattr(self.model, 'latent_trace', None), self.packed.t
+        trace, t = self.model.latent_trace, self.packed.t
         if trace is None:
             return
         host = lambda x: x.detach().cpu().numpy()
@@ -212,7 +212,7 @@ class LatentSchedule:
                 # from here on every iteration of the stage is the same launch sequence: capture it once, replay it n - it - 2 times
                 if use_graph and with_priors and it >= 1 and n - it - 1 >= 2 and not torch.cuda.is_current_stream_capturing():
                     try:
-                        if getattr(model, '_latent_capture_stream', None) is None:
+                        if model._latent_capture_stream is None:
                             model._latent_capture_stream = torch.cuda.Stream(device=dev)
                         graph = stepwise.capture_iteration(lambda: self.iteration(st, True, False), dev, model._latent_capture_stream)
                     except Exception as e:      # noqa: BLE001 -- the plain launches are always available

@@ -14,6 +14,7 @@ Division of labour:
 There is no CPU path for the device part: a missing library or a non-HIP device raises.
 """
 import contextlib
+import ctypes
 import os
 import time
 
@@ -51,9 +52,31 @@ _PERSON_KEYS = ('smpl_pose', 'smpl_beta', 'smpl_orient_cam', 'root_trans_cam', '
 
 
 class ResidentInputs:
-    """A batch of sequences in HBM as stage_inputs() leaves it: the HybrIK arrays on their frame rows (`g`), lengths, optional latent
-    draws, plus the host-side bookkeeping (person ids, sequence names) that never needs the device."""
-    pass
+    """A batch of sequences in HBM as stage_inputs() leaves it.
+    Geometry: S scenes x P person slots x T frames (the batch maxima); Ts, ids [per scene]: its length and its person ids; lens (S * P,): the length
+    of every slot's existing range (11 for an empty slot); exists {(scene, person id): `exist` array}.  Device arrays: g {'exist', 'rot', 'betas',
+    'trans', 'kp', 'K'}, the HybrIK arrays by (slot, frame); n_persons, seq_len (S,) and seq_len_slot (S * P,; 0 = an empty slot) int32.
+    meps (S * P, windows, NZ), teps (S * P, NZ): the caller's latents or None (init_resident draws).  meta [per scene]: seq_name, seq_len, gt,
+    gt_meta; explicit_seq_ids [per scene]: in_dict['seq_id'] or None.  latent_seq_ids, latent_person_ids, latent_seed_word: what the 'philox'
+    draw reads (_latent_table), None until a draw under 'philox' needs them.  validate: the value checks are still to run (value_checks clears
+    it); verdict (2, S * P) int32 on the device with its event verdict_ready, None before the checks and again after check_inputs; verdict_host
+    (pinned copy, event): set by _fetch_async, consumed by check_inputs.  upload_done: the event after the batch's host->device copies."""
+
+    def __init__(self, S, P, T, Ts, ids, lens, exists, g, n_persons, seq_len, seq_len_slot, meta, explicit_seq_ids, validate, meps=None, teps=None):
+        self.S, self.P, self.T, self.Ts, self.ids, self.lens, self.exists = S, P, T, Ts, ids, lens, exists
+        self.g, self.n_persons, self.seq_len, self.seq_len_slot, self.meps, self.teps = g, n_persons, seq_len, seq_len_slot, meps, teps
+        self.meta, self.explicit_seq_ids = meta, explicit_seq_ids
+        self.latent_seq_ids = self.latent_person_ids = self.latent_seed_word = None
+        self.validate, self.verdict, self.verdict_ready, self.verdict_host = bool(validate), None, None, None
+        self.upload_done = None               # (stage_inputs records it once everything above is on its way)
+
+    def raw_batch(self):
+        """glamr_raw_batch over the staged arrays."""
+        raw, g = _lib.RawBatch(), self.g
+        raw.n_slots, raw.max_len = self.S * self.P, self.T
+        for name, ten in (('seq_len', self.seq_len_slot), ('exist', g['exist']), ('rotmats', g['rot']), ('betas', g['betas']), ('root_trans', g['trans']), ('kp_2d', g['kp'])):
+            setattr(raw, name, ctypes.c_void_p(ten.data_ptr()))
+        return raw
 
 
 class LazyDict(dict):
@@ -139,7 +162,6 @@ class LazyDict(dict):
 
 def coschedule_enabled():
     """GLAMR_COSCHEDULE=0 switches the staggered two-stream pipeline (PipelineGate + GLAMR_NETS_COSCHEDULE kernels) off."""
-    import os
     return os.environ.get('GLAMR_COSCHEDULE', '1') != '0'
 
 
@@ -194,6 +216,9 @@ class ResidentGraph:
 
 
 class GlobalReconOptimizer:
+    # optimize_stream's two compute streams, made at its first call.  On the class, not in __init__: bench.py hands over its own two with
+    # `model.__dict__.setdefault('_compute_streams', ...)`, which an instance attribute set to None would turn into a no-op.
+    _compute_streams = None
 
     def __init__(self, cfg, device=torch.device('cuda'), log=None, smpl=None, mt_model=None, results_root='results'):
         self.cfg = cfg
@@ -211,6 +236,13 @@ class GlobalReconOptimizer:
         self.latent_seed = 0
         self._capture_split = None
         self._capture_head_split = None
+        # kept between calls, made at first use: the pinned staging sets (_staging), optimize_stream's copy stream, run_latent_schedule's capture stream
+        self._pinned = {'sets': [None, None], 'turn': 0}
+        self._download_stream = self._latent_capture_stream = None
+        self.kernel_ms = None                 # a list: collect() appends the duration of every stage launch of the batches it collects
+        self.last_losses = None               # (scenes, GLAMR_NUM_LOSSES): the loss values of the last batch collected
+        self.latent_graph_replays = 0         # run_latent_schedule: iterations of its last run that were graph replays
+        self.latent_trace = None              # a dict: run_latent_schedule records its first iteration with priors there (the parity tests)
         # Per-iteration loss log (:564,646-659).  The reference calls write_logs after EVERY optimizer.step -- with `log` None it prints.  Here
         # the iterations of a stage are one kernel launch: with a `log` (or keep_loss_history = True) the launch records the unweighted value of
         # every term at every iteration (glamr_scene_batch.loss_history; the plain instance with the reporting evaluation, about 2x the time),
@@ -274,31 +306,16 @@ class GlobalReconOptimizer:
         # extra_loss_schedule.ExtraLossSchedule with the built-in term (PenetrationTerm), beside a caller's extra_loss if one is set.  penetration_history[stage]:
         # (scenes, iterations) UNWEIGHTED values.  Without an entry in any stage nothing changes.
         self.flag_use_pen_loss = bool(g('flag_use_pen_loss', False))
-        packing.check_penetration(self.opt_stage_specs, self.specs)
-        self._pen_cfg = {}
-        for stage, spec in list(self.opt_stage_specs.items()):
-            rest, pen = packing.split_penetration(spec['loss_cfg'])
-            if pen is not None:
-                self._pen_cfg[stage] = pen
-                self.opt_stage_specs = dict(self.opt_stage_specs)
-                self.opt_stage_specs[stage] = dict(spec, loss_cfg=rest)
-        if self._pen_cfg:
-            extra_loss_schedule.check_supported(self.specs, what='the penetration term (loss_cfg)')
         self.penetration_history = {}
         # the six terms of packing.AUX_LOSS_IDS (cam_rot_smoothness ... local_traj_dheading_reg): taken off every stage's loss_cfg
         # like the penetration term and run by the same schedule (extra_loss_schedule.AuxTerms, one launch of glamr_grecon_aux_terms per
         # iteration).  aux_loss_history[stage][name]: (scenes, iterations) UNWEIGHTED values.  Without one of the names in any stage nothing changes.
-        packing.check_aux(self.opt_stage_specs, self.specs)
-        self._aux_cfg = {}
-        for stage, spec in list(self.opt_stage_specs.items()):
-            rest, aux = packing.split_aux(spec['loss_cfg'])
-            if aux is not None:
-                self._aux_cfg[stage] = aux
-                self.opt_stage_specs = dict(self.opt_stage_specs)
-                self.opt_stage_specs[stage] = dict(spec, loss_cfg=rest)
-        if self._aux_cfg:
-            extra_loss_schedule.check_supported(self.specs, what=extra_loss_schedule.aux_what({n for c in self._aux_cfg.values() for n in c}))
         self.aux_loss_history = {}
+        packing.check_penetration(self.opt_stage_specs, self.specs)
+        packing.check_aux(self.opt_stage_specs, self.specs)
+        self.opt_stage_specs, self._pen_cfg, self._aux_cfg = packing.split_off_kernel(self.opt_stage_specs)
+        if self._off_kernel_term() is not None:
+            extra_loss_schedule.check_supported(self.specs, what=self._off_kernel_term())
         self.flag_filter_pose = g('flag_filter_pose', True)
         # keypoint-count filter inside filter_pose (:50-52,264-268); with HybrIK's binary scores (14 scored joints per detected frame) it is all or
         # nothing: the reference's default minimum of 15 removes every frame, 14 or less none
@@ -325,18 +342,23 @@ class GlobalReconOptimizer:
             extra_loss_schedule.check_supported(self.specs)
         self._extra_loss = fn
 
+    def _off_kernel_term(self):
+        """None when the run has no term the stage kernel does not hold -- run_schedule serves it --, else the name a refusal gives what needs the
+        launch-by-launch schedule: the caller's term before the penetration term before the terms of packing.AUX_LOSS_IDS."""
+        return 'extra_loss' if self._extra_loss is not None else 'the penetration term (loss_cfg)' if self._pen_cfg else \
+            extra_loss_schedule.aux_what({n for c in self._aux_cfg.values() for n in c}) if self._aux_cfg else None
+
+    _WHY_OPTIMIZE_ONLY = {'extra_loss': 'while extra_loss is set: the term runs user Python in every iteration',
+                          'the penetration term (loss_cfg)': 'with the penetration term in loss_cfg: the term runs launch by launch on the skinned vertices'}
+
     def _refuse_extra_loss(self, what):
-        if self._extra_loss is not None:
-            raise NotImplementedError('%s while extra_loss is set: the term runs user Python in every iteration (optimize / optimize_batch only)' % what)
-        if self._pen_cfg:
-            raise NotImplementedError('%s with the penetration term in loss_cfg: the term runs launch by launch on the skinned vertices '
-                                      '(optimize / optimize_batch only)' % what)
-        if self._aux_cfg:
-            raise NotImplementedError('%s with %s: these terms run launch by launch on a kernel of their own (optimize / optimize_batch only)'
-                                      % (what, extra_loss_schedule.aux_what({n for c in self._aux_cfg.values() for n in c})))
+        term = self._off_kernel_term()
+        if term is not None:
+            why = self._WHY_OPTIMIZE_ONLY.get(term, 'with %s: these terms run launch by launch on a kernel of their own' % term)
+            raise NotImplementedError('%s %s (optimize / optimize_batch only)' % (what, why))
 
     def _run_schedule_or_extra(self, packed, max_iters, has_wd=False):
-        if self._extra_loss is None and not self._pen_cfg and not self._aux_cfg:
+        if self._off_kernel_term() is None:
             return self.run_schedule(packed, max_iters, has_wd=has_wd)
         return extra_loss_schedule.ExtraLossSchedule(self, packed).run(max_iters, has_wd=has_wd)
 
@@ -354,7 +376,7 @@ class GlobalReconOptimizer:
         seq_ids, person_ids = [], []
         for si, m in enumerate(rin.meta):
             # (an explicit in_dict['seq_id'] was noted by stage_inputs whatever the source was then: a batch staged under 'torch' draws the same)
-            sid = latent_rng.seq_id_for(dict(seq_name=m['seq_name'], seq_id=(getattr(rin, 'explicit_seq_ids', None) or [None] * len(rin.meta))[si]))
+            sid = latent_rng.seq_id_for(dict(seq_name=m['seq_name'], seq_id=rin.explicit_seq_ids[si]))
             for pi in range(rin.P):
                 seq_ids.append(sid)
                 person_ids.append(latent_rng.person_id_of(rin.ids[si][pi]) if pi < len(rin.ids[si]) else -1)
@@ -364,7 +386,7 @@ class GlobalReconOptimizer:
     def _draw_latents(self, rin, meps, teps):
         """glamr_latents_draw into (meps, teps) on the current stream.  Outside a capture the seed word is written first; a captured step holds
         the draw only and ResidentGraph.replay() writes the seed (so the seed can change between replays without re-capture)."""
-        if getattr(rin, 'latent_seq_ids', None) is None:
+        if rin.latent_seq_ids is None:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("this batch was staged under latent_source 'torch': stage_inputs() it again under 'philox' before capturing")
             self._latent_table(rin)
@@ -414,7 +436,7 @@ class GlobalReconOptimizer:
             d[key] = np.ascontiguousarray(d[key], dtype=np.float32)
         if self.flag_filter_pose:
             self._filter_pose(d)
-            if getattr(self, 'flag_make_invis_with_keypoint', False):                    # :264-268
+            if self.flag_make_invis_with_keypoint:                                        # :264-268
                 vis_ind = np.where(d['visible'] == 1.0)[0]
                 num_valid = (d['kp_2d_score'][vis_ind] > self.make_invis_keypoint_min_score).sum(axis=1)
                 d['visible'][vis_ind[num_valid < self.make_invis_keypoint_min_num]] = 0.0
@@ -530,13 +552,7 @@ class GlobalReconOptimizer:
             pose[k, :lens[k]] = d['smpl_pose_nofill'][ex]
             vis[k, :lens[k]] = d['visible'][ex]
         if latents is not None:
-            meps = np.zeros((len(flat), nw, NZ), np.float32)
-            teps = np.zeros((len(flat), NZ), np.float32)
-            for k, (si, idx, d) in enumerate(flat):
-                m = np.asarray(latents[si][idx]['motion'], np.float32)
-                meps[k, :m.shape[0]] = m
-                teps[k] = np.asarray(latents[si][idx]['traj'], np.float32).reshape(-1)
-            meps, teps = torch.from_numpy(meps).to(dev), torch.from_numpy(teps).to(dev)
+            meps, teps = packing.pack_latents(latents, [(si, idx) for si, idx, _ in flat], nw, NZ, dev)
         elif self.latent_source == 'philox':
             sids = [latent_rng.seq_id_for(d) for d in in_dicts]
             meps, teps = latent_rng.draw(self.latent_seed, [sids[si] for si, _, _ in flat], [latent_rng.person_id_of(idx) for _, idx, _ in flat], nw, dev)
@@ -593,7 +609,7 @@ class GlobalReconOptimizer:
         """Pinned host staging buffers for the HybrIK arrays, two sets used alternately (a set is rewritten only after the upload that
         last used it has finished).  Rows of frames without a detection keep whatever an earlier batch left there: the device
         preparation reads detection rows only (init.hip prep_person_kernel); `exist` and `K` are cleared because their other rows count."""
-        pool = self.__dict__.setdefault('_pinned', {'sets': [None, None], 'turn': 0})
+        pool = self._pinned
         i = pool['turn']
         pool['turn'] = 1 - i
         cur = pool['sets'][i]
@@ -610,19 +626,11 @@ class GlobalReconOptimizer:
             cur['np']['K'].fill(0.0)
         return cur
 
-    def _pool(self):
-        import concurrent.futures
-        p = self.__dict__.get('_thread_pool')
-        if p is None:
-            p = self.__dict__['_thread_pool'] = concurrent.futures.ThreadPoolExecutor(max_workers=8)
-        return p
-
     def _scatter_inputs(self, in_dicts, ids, P, h):
         """Per-detection HybrIK arrays -> their frame rows in the staging arrays `h` (numpy views): glamr_host_scatter, a few host threads
         doing block copies without the GIL (numpy on one thread took 60-130 ms per 1024 sequences depending on the box, a Python thread
         pool was slower still).  This loop only collects the ten numbers per person the library needs.  Returns (seq_len per slot,
         length of the existing range per slot, {(sequence, person id): exist array})."""
-        import ctypes
         n_slots = len(in_dicts) * P
         T = h['exist'].shape[1]
         seq_len_slot = np.zeros(n_slots, np.int32)
@@ -681,34 +689,20 @@ class GlobalReconOptimizer:
         stg = self._staging(n_slots, T)
         h = stg['np']
         seq_len_slot, lens, exists = self._scatter_inputs(in_dicts, ids, P, h)
-        rin = ResidentInputs()
-        rin.S, rin.P, rin.T, rin.Ts, rin.ids, rin.lens, rin.exists = S, P, T, Ts, ids, lens, exists
-        rin.g = {k: v.to(dev, non_blocking=True) for k, v in stg['t'].items()}
-        rin.n_persons = torch.tensor([len(x) for x in ids], dtype=torch.int32).to(dev, non_blocking=True)
-        rin.seq_len = torch.tensor(Ts, dtype=torch.int32).to(dev, non_blocking=True)
-        rin.seq_len_slot = torch.from_numpy(seq_len_slot).to(dev, non_blocking=True)
-        rin.meps = rin.teps = None
+        up = lambda x: x.to(dev, non_blocking=True)
+        rin = ResidentInputs(S, P, T, Ts, ids, lens, exists, g={k: up(v) for k, v in stg['t'].items()},
+                             n_persons=up(torch.tensor([len(x) for x in ids], dtype=torch.int32)), seq_len=up(torch.tensor(Ts, dtype=torch.int32)),
+                             seq_len_slot=up(torch.from_numpy(seq_len_slot)), validate=validate, explicit_seq_ids=[d.get('seq_id') for d in in_dicts],
+                             meta=[{'seq_name': d['seq_name'], 'seq_len': Ts[si], 'gt': d.get('gt', {}), 'gt_meta': d.get('gt_meta', {})} for si, d in enumerate(in_dicts)])
         if latents is not None:
-            nw = num_windows(int(lens.max()))
-            meps = np.zeros((n_slots, nw, NZ), np.float32)
-            teps = np.zeros((n_slots, NZ), np.float32)
-            for si in range(S):
-                for pi, idx in enumerate(ids[si]):
-                    m = np.asarray(latents[si][idx]['motion'], np.float32)
-                    meps[si * P + pi, :m.shape[0]] = m
-                    teps[si * P + pi] = np.asarray(latents[si][idx]['traj'], np.float32).reshape(-1)
-            rin.meps, rin.teps = torch.from_numpy(meps).to(dev), torch.from_numpy(teps).to(dev)
-        rin.meta = [{'seq_name': d['seq_name'], 'seq_len': Ts[si], 'gt': d.get('gt', {}), 'gt_meta': d.get('gt_meta', {})} for si, d in enumerate(in_dicts)]
-        rin.latent_seq_ids = rin.latent_person_ids = rin.latent_seed_word = None
-        rin.explicit_seq_ids = [d.get('seq_id') for d in in_dicts]
+            slots = [(si, ids[si][pi]) if pi < len(ids[si]) else None for si in range(S) for pi in range(P)]
+            rin.meps, rin.teps = packing.pack_latents(latents, slots, num_windows(int(lens.max())), NZ, dev)
         if self.latent_source == 'philox' and latents is None:
             self._latent_table(rin)                          # (uploaded with the rest of the batch: before `upload_done`)
         # one event for "uploaded", on the stream this call ran on: the staging set is rewritten only after it and a pipelined caller's compute
         # stream waits for it.  The VALUE checks of the wire format run on the device later, on the stream that consumes the batch
         # (value_checks(), called by init_resident): as kernels of the upload stream they gated `upload_done` while competing for CUs with
         # the previous batch's optimiser stage -- a pipelined caller's next batch started 15 ms late.
-        rin.verdict = None
-        rin.validate = bool(validate)
         stg['event'] = torch.cuda.Event()
         stg['event'].record()
         rin.upload_done = stg['event']
@@ -721,15 +715,10 @@ class GlobalReconOptimizer:
         quaternions, demo.py:320): glamr_check_inputs, ONE pass over the uploaded arrays on the current stream (the torch expressions it
         replaces were 5 ms of reductions per 1024 sequences), once per ResidentInputs; the verdict (2, n_slots) stays on the device until
         check_inputs() / collect() reads it."""
-        if not getattr(rin, 'validate', False) or rin.verdict is not None:
+        if not rin.validate or rin.verdict is not None:
             return
-        import ctypes
-        n_slots, T, g = rin.S * rin.P, rin.T, rin.g
-        raw = _lib.RawBatch()
-        raw.n_slots, raw.max_len = n_slots, T
-        for name, ten in (('seq_len', rin.seq_len_slot), ('exist', g['exist']), ('rotmats', g['rot']), ('betas', g['betas']), ('root_trans', g['trans']), ('kp_2d', g['kp'])):
-            setattr(raw, name, ctypes.c_void_p(ten.data_ptr()))
-        verdict = torch.empty((2, n_slots), dtype=torch.int32, device=g['exist'].device)
+        raw, g = rin.raw_batch(), rin.g
+        verdict = torch.empty((2, raw.n_slots), dtype=torch.int32, device=g['exist'].device)
         _lib.check(_lib.lib().glamr_check_inputs(ctypes.byref(raw), _lib.ptr(g['K']), _lib.ptr(verdict), _lib.current_stream()))
         rin.verdict = verdict                                                                    # (2, n_slots) on the device
         rin.verdict_ready = torch.cuda.Event()
@@ -742,14 +731,14 @@ class GlobalReconOptimizer:
 
     def check_inputs(self, rin):
         """Raises WireFormatError for the first person whose uploaded arrays failed the value checks (one small device->host copy)."""
-        if getattr(rin, 'verdict', None) is None:
-            if getattr(rin, 'validate', False) and not torch.cuda.is_current_stream_capturing():
+        if rin.verdict is None:
+            if rin.validate and not torch.cuda.is_current_stream_capturing():
                 self.value_checks(rin)                                  # a batch nobody has checked yet (its only uses so far were graph replays)
-            if getattr(rin, 'verdict', None) is None:
+            if rin.verdict is None:
                 return
         from glamr_amd.utils import wire
-        hv = getattr(rin, 'verdict_host', None)
-        if hv is not None:                                              # (copied with the batch's results: _fetch_async)
+        hv = rin.verdict_host
+        if hv is not None:                                             # (copied with the batch's results: _fetch_async)
             hv[1].synchronize()
             v = hv[0].numpy()
             rin.verdict_host = None
@@ -767,12 +756,7 @@ class GlobalReconOptimizer:
     def _init_prepare(self, rin, packed, pa_t):
         """glamr_init_prepare on the staged batch: visibility bookkeeping, rotation matrices -> axis-angle, interpolation over detection gaps,
         filter_pose (:88-148,250-271).  Returns the structures the following launches share."""
-        import ctypes
-        L, g, n_slots, T = _lib.lib(), rin.g, rin.S * rin.P, rin.T
-        raw = _lib.RawBatch()
-        raw.n_slots, raw.max_len = n_slots, T
-        for name, ten in (('seq_len', rin.seq_len_slot), ('exist', g['exist']), ('rotmats', g['rot']), ('betas', g['betas']), ('root_trans', g['trans']), ('kp_2d', g['kp'])):
-            setattr(raw, name, ctypes.c_void_p(ten.data_ptr()))
+        L, n_slots, T, raw = _lib.lib(), rin.S * rin.P, rin.T, rin.raw_batch()
         pa = _lib.PersonArrays()
         for name, ten in pa_t.items():
             setattr(pa, name, ctypes.c_void_p(ten.data_ptr()))
@@ -801,7 +785,6 @@ class GlobalReconOptimizer:
         """init_data (:76-248) on device-resident inputs: per-person preparation, motion priors, scene assembly, cached joints and
         the 'init' forward pass -- kernel launches only, nothing crosses PCIe.  Returns (datas, packed): `datas` are light
         per-sequence dictionaries that collect() completes from the device arrays."""
-        import ctypes
         t1 = time.time()
         dev, L = self.device, _lib.lib()
         S, P, T, g = rin.S, rin.P, rin.T, rin.g
@@ -838,23 +821,20 @@ class GlobalReconOptimizer:
                 self._capture_head_split()                             # capture_resident under a gate: the first cut (replay() waits for the gate there)
             elif not torch.cuda.is_current_stream_capturing():
                 gate.before(torch.cuda.current_stream(dev))
-        # the latent draws of the motion priors (given latents: copied into the priors' fixed arrays)
-        if rs:
-            meps, teps = rs['meps'], rs['teps']
-            if rin.meps is not None:
+        # the latent draws of the motion priors.  Where they live: the priors' fixed arrays when there is a resident set, else the caller's own
+        # tensors or fresh ones.  What fills them: the caller's latents, the library's Philox streams, or torch.randn (motion, then trajectory).
+        given = rin.meps is not None
+        meps, teps = (rs['meps'], rs['teps']) if rs else (rin.meps, rin.teps) if given else \
+            (torch.empty((n_slots, nw, NZ), device=dev), torch.empty((n_slots, NZ), device=dev))
+        if given:
+            if rs:
                 meps.copy_(rin.meps)
                 teps.copy_(rin.teps)
-            elif self.latent_source == 'philox':
-                self._draw_latents(rin, meps, teps)
-            else:
-                torch.randn(meps.shape, out=meps)
-                torch.randn(teps.shape, out=teps)
-        elif rin.meps is None and self.latent_source == 'philox':
-            meps, teps = torch.empty((n_slots, nw, NZ), device=dev), torch.empty((n_slots, NZ), device=dev)
+        elif self.latent_source == 'philox':
             self._draw_latents(rin, meps, teps)
         else:
-            meps = rin.meps if rin.meps is not None else torch.randn((n_slots, nw, NZ), device=dev)
-            teps = rin.teps if rin.teps is not None else torch.randn((n_slots, NZ), device=dev)
+            torch.randn(meps.shape, out=meps)
+            torch.randn(teps.shape, out=teps)
         # motion priors on every person of every sequence in one call
         def open_gate():
             if self._capture_split is not None:
@@ -927,7 +907,7 @@ class GlobalReconOptimizer:
                 hbuf.copy_(v, non_blocking=True)
                 host[k] = hbuf
             hv = None
-            if rin is not None and getattr(rin, 'verdict', None) is not None:
+            if rin is not None and rin.verdict is not None:
                 # the wire-format verdict rides along (a blocking .cpu() of its own was 7 ms of host stall per batch: tools/host_profile.py)
                 torch.cuda.current_stream(self.device).wait_event(rin.verdict_ready)
                 hv = torch.empty(rin.verdict.shape, dtype=rin.verdict.dtype, pin_memory=True)
@@ -941,7 +921,7 @@ class GlobalReconOptimizer:
     def _materialise(self, datas, packed, stage_vars, fetched=None):
         """Builds the reference-style output dictionaries (numpy) from the device arrays: ONE device->host copy per array; per person, plain
         slices of the batch arrays right away and the converted ones (float64 masks / keypoints, 4 x 4 matrices, frame tables) on access."""
-        P, T, l = packed.P, packed.T, packed.layout
+        P, l = packed.P, packed.layout
         if fetched is None:
             fetched = self._fetch_async(packed)
         host, ev = fetched
@@ -963,24 +943,20 @@ class GlobalReconOptimizer:
         def person_factory(k, pi, si, Ts):
             fs, fe = fr_start[k], fr_end[k]
             n = fe - fs
-            pp = h['params'][si, l['person0'] + pi * l['person_stride']:l['person0'] + (pi + 1) * l['person_stride']]
             frame = lambda name: (lambda: h[name][k, :Ts])
-            cut = {
+            var = lambda name: (lambda: packing.person_view(h['params'][si], l, pi, name)[packing.var_rows(name, n, Ts)])
+            cut = {name: var(name) for name in packing.PERSON_VARS}
+            cut.update({
                 'smpl_pose': frame('pa_smpl_pose'), 'smpl_beta': frame('pa_smpl_beta'), 'smpl_orient_cam': frame('orient_cam'), 'root_trans_cam': frame('pa_trans_cam'),
                 'cam_K': lambda: h['cam_K'][k, :Ts].reshape(Ts, 3, 3), 'traj_local_pred': lambda: h['traj_local_pred'][k, :n],
                 'smpl_orient_world_base': frame('base_orient'), 'root_trans_world_base': frame('base_trans'), 'smpl_orient_world': frame('orient_world'),
                 'root_trans_world': frame('trans_world'), 'kp_2d_pred': frame('kp_2d_pred'), 'smpl_orient_cam_in_world': frame('orient_cam_in_world'),
-                'traj_local_xy': lambda: pp[l['local_xy']:l['local_xy'] + 2], 'traj_local_heading': lambda: pp[l['local_heading']:l['local_heading'] + 1],
-                'traj_local_dxy': lambda: pp[l['local_dxy']:l['local_dxy'] + 2 * T].reshape(T, 2)[1:n],
-                'traj_local_dheading': lambda: pp[l['local_dheading']:l['local_dheading'] + T][1:n],
-                'traj_local_z': lambda: pp[l['local_z']:l['local_z'] + T][:n], 'traj_local_rot': lambda: pp[l['local_rot']:l['local_rot'] + 6 * T].reshape(T, 6)[:n],
-                'world_dheading': lambda: pp[l['world_dheading']:l['world_dheading'] + T][:Ts, None],
                 'visible': lambda: h['vis'][k, :Ts].astype(np.float64), 'visible_orig': lambda: h['pa_visible_orig'][k, :Ts].astype(np.float64),
                 'frames': lambda: np.arange(Ts), 'vis_frames': lambda: h['vis'][k, :Ts] == 1, 'invis_frames': lambda: h['vis'][k, :Ts] == 0,
                 'frame2ind': lambda: {f: f for f in range(Ts)},
                 'kp_2d': lambda: h['kp_2d'][k, :Ts].astype(np.float64), 'kp_2d_aligned': lambda: h['kp_2d'][k, :Ts].astype(np.float64),
                 'kp_2d_score': lambda: h['kp_score'][k, :Ts].astype(np.float64), 'person2cam': lambda: to44(h['person2cam'][k, :Ts]),
-            }
+            })
 
             def exist_frames():
                 e = np.zeros(Ts, bool)
@@ -992,7 +968,6 @@ class GlobalReconOptimizer:
         has_cam = 'cam' in stage_vars
         scene_keys = ('cam_pose', 'cam_pose_inv', 'fr_num_persons', 'cam_inv_rot_residual', 'rel_transform_cam', 'cam_inv_trans_residual') + \
             ((('cam_rot_6d_fix', 'cam_trans_fix') if fixed_cam else ('cam_rot_6d', 'cam_trans')) if has_cam else ())
-        o_r6, o_tr, o_rres, o_tres = l['cam_rot6d'], l['cam_trans'], l['cam_inv_rot_res'], l['cam_inv_trans_res']
         h_vis, h_params, h_cam = h['vis'], h['params'], h['cam_pose']
         person_ids = packed.person_ids
 
@@ -1005,20 +980,16 @@ class GlobalReconOptimizer:
             def num_persons():
                 return sum((h_vis[si * P + pi, :Ts] == 1).astype(np.int64) for pi in range(n_p))
 
-            def rot_residual():
-                empty = np.where(num_persons() == 0)[0]
-                return prm[o_rres:o_rres + 6 * T].reshape(T, 6)[empty]
-
             def rel_dict():
                 if rel is None:
                     return {}
                 return {(i, j): to44(rel[si, i, j, :Ts]) for i in range(n_p) for j in range(n_p) if i != j}
-            r6 = lambda: prm[o_r6:o_r6 + 6 * T].reshape(T, 6)
-            tr = lambda: prm[o_tr:o_tr + 3 * T].reshape(T, 3)
-            cut = {'cam_pose': lambda: to44(cam12), 'cam_pose_inv': lambda: nt.invert_transform(to44(cam12)), 'fr_num_persons': num_persons,
-                   'cam_inv_rot_residual': rot_residual, 'rel_transform_cam': rel_dict,
-                   'cam_inv_trans_residual': lambda: prm[o_tres:o_tres + 3 * T].reshape(T, 3)[:Ts],
-                   'cam_rot_6d_fix': lambda: r6()[:1], 'cam_trans_fix': lambda: tr()[:1], 'cam_rot_6d': lambda: r6()[:Ts], 'cam_trans': lambda: tr()[:Ts]}
+            # (`empty` is only worked out for the variable whose rows it is)
+            var = lambda name: (lambda: packing.scene_view(prm, l, name)[packing.var_rows(
+                name, Ts=Ts, empty=np.where(num_persons() == 0)[0] if name == 'cam_inv_rot_residual' else None)])
+            cut = {name: var(name) for name in packing.SCENE_VARS}
+            cut.update({'cam_pose': lambda: to44(cam12), 'cam_pose_inv': lambda: nt.invert_transform(to44(cam12)), 'fr_num_persons': num_persons,
+                        'rel_transform_cam': rel_dict})
             return lambda key: cut[key]()
         for si, d in enumerate(datas):
             Ts = d['seq_len']
@@ -1065,7 +1036,6 @@ class GlobalReconOptimizer:
     @staticmethod
     def launch_ms(ws):
         """Duration of the stage launch that used workspace `ws`, from the kernel's own clock (blocks until it has finished)."""
-        import ctypes
         ns = ctypes.c_double()
         _lib.check(_lib.lib().glamr_grecon_last_launch_ns(_lib.ptr(ws), ctypes.byref(ns)))
         return ns.value * 1e-6
@@ -1123,14 +1093,12 @@ class GlobalReconOptimizer:
         fr_start = packed.t['fr_start'].view(S, P).long()
         keep = torch.ones_like(packed.t['params'])
         t_idx = torch.arange(T, device=packed.device)
+        s_idx = torch.arange(S, device=packed.device)[:, None].expand(S, T)
         for pi in range(P):
             # the residual of video frame t sits at row t - fr_start of the person's block (rows of frames before fr_start do not exist)
             e = t_idx[None, :] - fr_start[:, pi:pi + 1]                                        # (S, T)
-            col = l['person0'] + pi * l['person_stride'] + l['local_rot'] + e * 6
             ok = (~vis[:, pi]) & (e >= 0)
-            s_idx = torch.arange(S, device=packed.device)[:, None].expand(S, T)
-            for k in range(6):
-                keep[s_idx[ok], (col + k)[ok]] = 0.0
+            packing.person_view(keep, l, pi, 'traj_local_rot')[s_idx[ok], e[ok]] = 0.0         # (S, T, 6): all six numbers of the row
 
         def hook(packed_, stage, spec, grads):
             grads.mul_(keep)
@@ -1143,12 +1111,11 @@ class GlobalReconOptimizer:
         """HBM in, HBM out: init_data + the full schedule on a ResidentInputs batch.  Returns (datas, packed) with every result
         (optimised variables, world trajectories, projections, camera) in packed.t on the device; collect() brings them to the host."""
         self._refuse_extra_loss('optimize_resident')
+        datas, packed = self.init_resident(rin, init_forward=self.latent_mode or not self._schedule_overwrites_init())
         if self.latent_mode:
-            datas, packed = self.init_resident(rin, init_forward=True)
             self.run_latent_schedule(rin, packed, max_iters)
-            return datas, packed
-        datas, packed = self.init_resident(rin, init_forward=not self._schedule_overwrites_init())
-        self.run_schedule(packed, max_iters)
+        else:
+            self.run_schedule(packed, max_iters)
         return datas, packed
 
     def capture_resident(self, rin, max_iters=None, stream=None, check=True):
@@ -1164,7 +1131,7 @@ class GlobalReconOptimizer:
         # the value checks of the wire format run once per batch, outside a capture (init_resident skips them while capturing): a batch whose
         # FIRST use is this capture is checked here -- the verdict surfaces in collect() / check_inputs() as usual
         self.value_checks(rin)
-        if self.latent_source == 'philox' and rin.meps is None and getattr(rin, 'latent_seq_ids', None) is None:
+        if self.latent_source == 'philox' and rin.meps is None and rin.latent_seq_ids is None:
             self._latent_table(rin)                                   # (a batch staged under 'torch': its table is uploaded here, outside the capture)
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
         if st == torch.cuda.default_stream(self.device):
@@ -1212,7 +1179,7 @@ class GlobalReconOptimizer:
                     self._capture_head_split = None
                 tail.capture_end()
             rg = ResidentGraph(graph, datas, packed, st, tail=tail, gate=self.pipeline_gate, head=head)
-        philox = getattr(rin, 'latent_seed_word', None) is not None and rin.meps is None and self.latent_source == 'philox'
+        philox = rin.latent_seed_word is not None and rin.meps is None and self.latent_source == 'philox'
         if philox:
             # the captured draw reads its seed from the batch's seed word: every replay first writes the model's CURRENT latent_seed there
             rg.before_replay = lambda: latent_rng.set_seed(rin.latent_seed_word, self.latent_seed)
@@ -1259,8 +1226,7 @@ class GlobalReconOptimizer:
         else:
             torch.cuda.synchronize(self.device)
             t0 = time.time()
-            all_vars = self._all_vars()
-            packed.unpack_into(datas, {'opt_variables': all_vars} if self.opt_stage_specs else None, self.specs, as_torch=False)
+            packed.unpack_into(datas, {'opt_variables': self._all_vars()} if self.opt_stage_specs else None, self.specs, as_torch=False)
             self.last_losses = packed.t['losses'].cpu().numpy()
         if self.latent_mode and packed.latents is not None and rin is not None:
             # the optimised draws, per person as the reference keeps them in pose_dict (:155-158)
@@ -1270,7 +1236,7 @@ class GlobalReconOptimizer:
                     k = si * packed.P + pi
                     d['person_data'][idx]['motion_latent'] = meps[k, :num_windows(int(rin.lens[k]))].copy()
                     d['person_data'][idx]['traj_latent'] = teps[k][None].copy()
-        if getattr(self, 'kernel_ms', None) is not None and packed.stage_ws:
+        if self.kernel_ms is not None and packed.stage_ws:
             self.kernel_ms.extend(self.launch_ms(ws) for ws in packed.stage_ws)
         self.timings['unpack'] = time.time() - t0
         return datas
@@ -1289,7 +1255,9 @@ class GlobalReconOptimizer:
     def _optimize_stream(self, batches, latents, max_iters):
         dev = self.device
         # consecutive batches alternate over two compute streams (the launch seams and tails of one batch are covered by the next, as in bench.py)
-        computes = self.__dict__.setdefault('_compute_streams', [torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)])
+        if self._compute_streams is None:
+            self._compute_streams = [torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)]
+        computes = self._compute_streams
         # Uploads and downloads share ONE third stream.  Not more: the runtime multiplexes HIP streams onto 4 hardware queues, and with a
         # separate upload stream (5 streams with the default one) two of them shared a queue -- a batch then started only when the previous one
         # had finished (tools/stream_timeline.py; raising GPU_MAX_HW_QUEUES to 8, three compute streams and the default stream as the uploader
@@ -1297,7 +1265,9 @@ class GlobalReconOptimizer:
         # before last, so every batch began with 7 ms of PCIe and nothing else (50.5 ms from batch to batch against 43.4 resident).  On the
         # copy stream the order of the enqueues is what matters: a download waits for its batch's event, and an upload enqueued behind it
         # waits too -- _stream_loop enqueues a batch's download only when the upload of the batch two later is already in the queue.
-        down = self.__dict__.setdefault('_download_stream', torch.cuda.Stream(device=dev))
+        if self._download_stream is None:
+            self._download_stream = torch.cuda.Stream(device=dev)
+        down = self._download_stream
         it = iter(batches)
         lat = iter(latents) if latents is not None else None
         turn = [0]
@@ -1346,7 +1316,7 @@ class GlobalReconOptimizer:
             turn[0] += 1
             compute.wait_event(rin.upload_done)
             with torch.cuda.stream(compute):
-                datas, packed = self.optimize_resident(rin, max_iters) if self.latent_mode else self._resident_for_stream(rin, max_iters)
+                datas, packed = self.optimize_resident(rin, max_iters)      # (optimize_stream has refused what it refuses)
                 done = torch.cuda.Event()
                 done.record()
             flight.append((datas, packed, done))
@@ -1356,11 +1326,6 @@ class GlobalReconOptimizer:
                 yield self.collect(*fetch(flight.pop(0)))              # (enqueued only now: a download waiting for its batch must not sit in front of that upload)
         while flight:
             yield self.collect(*fetch(flight.pop(0)))
-
-    def _resident_for_stream(self, rin, max_iters):
-        datas, packed = self.init_resident(rin, init_forward=not self._schedule_overwrites_init())
-        self.run_schedule(packed, max_iters)
-        return datas, packed
 
     def optimize_batch(self, in_dicts, latents=None, max_iters=None):
         """Host dictionaries in, host dictionaries out (optimize() of the reference for a batch of independent sequences)."""
@@ -1377,16 +1342,6 @@ class GlobalReconOptimizer:
         self.timings['optimise'] = time.time() - t0
         return self.collect(datas, packed)
 
-    @staticmethod
-    def _to_numpy(x):
-        if isinstance(x, torch.Tensor):
-            return x.detach().cpu().numpy()
-        if isinstance(x, dict):
-            return {k: GlobalReconOptimizer._to_numpy(v) for k, v in x.items()}
-        if isinstance(x, list):
-            return [GlobalReconOptimizer._to_numpy(v) for v in x]
-        return x
-
     # -- reference entry points ---------------------------------------------------------------------------------------------------
     def init_data(self, in_dict, latents=None):
         datas, packed = self.init_data_batch([in_dict], None if latents is None else [latents])
@@ -1402,7 +1357,6 @@ class GlobalReconOptimizer:
     def continue_batch(self, datas, max_iters=None):
         """optimize(in_dict, continue_opt=True) (:572-573): `in_dict` is the dictionary a previous optimize() returned; the schedule
         runs again from its variables.  The inputs are not modified."""
-        import copy
         datas = [dict(d, person_data={i: dict(pd) for i, pd in d['person_data'].items()}) for d in datas]
         j_locals = []
         for d in datas:

@@ -2,6 +2,7 @@
 global_recon/models/global_recon_model.py:217-230) into the flat, padded arrays of `glamr_scene_batch` (include/glamr_hip.h)
 and back.  Pure layout code: no reference arithmetic happens here."""
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -101,6 +102,22 @@ def check_aux(opt_stage_specs, model_specs):
                                  "in a stage that optimises them (a KeyError in the reference, or the stale tensor of an earlier stage)" % (name, stage))
 
 
+def split_off_kernel(opt_stage_specs):
+    """opt_stage_specs -> (the specs the stage kernel is given: every stage's loss_cfg without the penetration term and the terms of AUX_LOSS_IDS,
+    {stage: split_penetration's second result}, {stage: split_aux's}) -- the stages that list none are left out.  Without such an entry anywhere
+    the first result IS the argument; otherwise one new dictionary (the argument is not modified)."""
+    rest_specs, pen_cfg, aux_cfg = {}, {}, {}
+    for stage, spec in opt_stage_specs.items():
+        rest, pen = split_penetration(spec['loss_cfg'])
+        rest, aux = split_aux(rest)
+        if pen is not None:
+            pen_cfg[stage] = pen
+        if aux is not None:
+            aux_cfg[stage] = aux
+        rest_specs[stage] = spec if rest is spec['loss_cfg'] else dict(spec, loss_cfg=rest)
+    return (rest_specs if pen_cfg or aux_cfg else opt_stage_specs), pen_cfg, aux_cfg
+
+
 def aux_desc(aux_cfg):
     """split_aux's second result -> glamr_aux_desc."""
     ad = _lib.AuxDesc()
@@ -131,6 +148,64 @@ def param_layout_py(max_persons, max_len):
     l['person_stride'] = l['world_dheading'] + T
     l['scene_stride'] = l['person0'] + max_persons * l['person_stride']
     return l
+
+
+# The variables of a scene's params row under the reference's tensor names (global_recon_model.py:396-426,459-480): name -> (key of param_layout_py,
+# shape of one frame's entry, rows).  `rows(n, Ts, empty)` picks the frames the reference tensor holds out of the max_len rows of the variable's
+# block -- n: the person's existing frames, Ts: the scene's length, empty: the indices of the frames nobody is seen in --; None: the variable has
+# no frame axis.  Everything that reads or writes a variable of a row goes through person_view / scene_view and var_rows.
+_EXISTING, _STEPS, _SCENE, _FIRST = (lambda n, Ts, empty: slice(n)), (lambda n, Ts, empty: slice(1, n)), (lambda n, Ts, empty: slice(Ts)), (lambda n, Ts, empty: slice(1))
+PERSON_VARS = {'traj_local_xy': ('local_xy', (2,), None), 'traj_local_heading': ('local_heading', (1,), None),
+               'traj_local_dxy': ('local_dxy', (2,), _STEPS), 'traj_local_dheading': ('local_dheading', (), _STEPS),
+               'traj_local_z': ('local_z', (), _EXISTING), 'traj_local_rot': ('local_rot', (6,), _EXISTING),
+               'world_dheading': ('world_dheading', (1,), _SCENE)}
+SCENE_VARS = {'cam_rot_6d': ('cam_rot6d', (6,), _SCENE), 'cam_trans': ('cam_trans', (3,), _SCENE),
+              'cam_rot_6d_fix': ('cam_rot6d', (6,), _FIRST), 'cam_trans_fix': ('cam_trans', (3,), _FIRST),      # flag_fixed_cam: frame 0's entry is the variable
+              'cam_inv_rot_residual': ('cam_inv_rot_res', (6,), lambda n, Ts, empty: empty), 'cam_inv_trans_residual': ('cam_inv_trans_res', (3,), _SCENE)}
+
+
+def var_rows(name, n=None, Ts=None, empty=None):
+    """The index into a variable's view (person_view / scene_view) that cuts the reference tensor `name`."""
+    rows = (PERSON_VARS.get(name) or SCENE_VARS[name])[2]
+    return slice(None) if rows is None else rows(n, Ts, empty)
+
+
+def _var_view(block, layout, table, name):
+    key, shape, rows = table[name]
+    frames = () if rows is None else (layout['cam_trans'] // 6,)      # max_len: cam_rot6d holds 6 numbers per frame
+    v = block[..., layout[key]:layout[key] + math.prod(frames + shape)]
+    return v.reshape(tuple(v.shape[:-1]) + frames + shape)
+
+
+def person_cols(layout, pi):
+    """The columns of person slot `pi` in a params row."""
+    return slice(layout['person0'] + pi * layout['person_stride'], layout['person0'] + (pi + 1) * layout['person_stride'])
+
+
+def person_view(row, layout, pi, name=None):
+    """A VIEW of person slot `pi`'s block of `row` -- a params row (scene_stride,) or any array (..., scene_stride) of them, numpy or torch: only
+    the last axis is cut -- or, with `name`, of one variable of PERSON_VARS in it: (..., max_len) + the frame's shape, (...,) + shape without a frame axis."""
+    block = row[..., person_cols(layout, pi)]
+    return block if name is None else _var_view(block, layout, PERSON_VARS, name)
+
+
+def scene_view(row, layout, name=None):
+    """A VIEW of the camera block of `row` (as person_view), or of one variable of SCENE_VARS in it."""
+    return row[..., :layout['person0']] if name is None else _var_view(row, layout, SCENE_VARS, name)
+
+
+def pack_latents(latents, rows, n_windows, width, device):
+    """Caller-given latents ([per sequence] {person id: {'motion': (windows, width), 'traj': (1, width)}}) -> (len(rows), n_windows, width) and
+    (len(rows), width) on `device`, for rows [(sequence, person id), or None: an empty slot, zeros]; a person's unused windows stay zero."""
+    meps = np.zeros((len(rows), n_windows, width), np.float32)
+    teps = np.zeros((len(rows), width), np.float32)
+    for k, row in enumerate(rows):
+        if row is not None:
+            lat = latents[row[0]][row[1]]
+            m = np.asarray(lat['motion'], np.float32)
+            meps[k, :m.shape[0]] = m
+            teps[k] = np.asarray(lat['traj'], np.float32).reshape(-1)
+    return torch.from_numpy(meps).to(device), torch.from_numpy(teps).to(device)
 
 
 def stage_desc(stage_specs, model_specs, has_world_dheading=False, niters=None):
@@ -183,7 +258,6 @@ def stage_desc(stage_specs, model_specs, has_world_dheading=False, niters=None):
 
 def carve_zeros(spec, device):
     """{name: zero tensor} for [(name, dtype, shape)] of 4-byte dtypes, all views of ONE zero-filled device allocation (64-float aligned)."""
-    import math
     offs, total = [], 0
     for _, _, shape in spec:
         offs.append(total)
@@ -198,8 +272,6 @@ def carve_zeros(spec, device):
 
 class PackedScenes:
     """Flat tensors of a batch of scenes on `device` + the ctypes struct that points at them."""
-
-    INT_FIELDS = ('n_persons', 'seq_len', 'fr_start', 'fr_end')
 
     def _declare(self, device, S, P, T, seq_names=None):
         """The geometry, and what a batch carries beside its arrays -- set by whoever has it, None / [] until then: person_arrays (the per-person
@@ -261,6 +333,7 @@ class PackedScenes:
             t['rel_transform_cam'] = f32(S, P, P, T, 12)
         cpu = lambda x: torch.as_tensor(x).detach().to('cpu')
         l = self.layout
+        rtc = f32(S * P, T, 3) if all('root_trans_cam' in pd for d in datas for pd in d['person_data'].values()) else None
         for si, d in enumerate(datas):
             ids = self.person_ids[si]
             Ts = int(d['seq_len'])
@@ -270,11 +343,10 @@ class PackedScenes:
             npers = cpu(d['fr_num_persons'])
             empty = torch.where(npers == 0)[0]
             if len(empty) and 'cam_inv_rot_residual' in d:
-                prm[l['cam_inv_rot_res']:l['cam_inv_rot_res'] + 6 * T].view(T, 6)[empty] = cpu(d['cam_inv_rot_residual']).float()
+                scene_view(prm, l, 'cam_inv_rot_residual')[empty] = cpu(d['cam_inv_rot_residual']).float()
             res = cpu(d['cam_inv_trans_residual']).float()
-            tr = prm[l['cam_inv_trans_res']:l['cam_inv_trans_res'] + 3 * T].view(T, 3)
             if res.shape[0] == Ts:
-                tr[:Ts] = res
+                scene_view(prm, l, 'cam_inv_trans_residual')[var_rows('cam_inv_trans_residual', Ts=Ts)] = res
             elif len(empty):
                 raise NotImplementedError('flag_cam_inv_trans_res_all=False is not supported')
             for pi, idx in enumerate(ids):
@@ -292,43 +364,30 @@ class PackedScenes:
                 t['base_orient'][slot, :Ts] = cpu(pd['smpl_orient_world_base']).float()
                 t['base_trans'][slot, :Ts] = cpu(pd['root_trans_world_base']).float()
                 t['person2cam'][slot, :Ts] = cpu(pd['person2cam'])[:, :3, :].reshape(Ts, 12).float()
+                if rtc is not None:
+                    rtc[slot, :Ts] = cpu(pd['root_trans_cam']).float()
                 if need_mask:
                     m = torch.ones(n - 1)
                     for (s, e) in cam_fix_frames:
                         m[s:e] = 0.0
                     t['dheading_mask'][slot, 1:n] = m
-                pp = prm[l['person0'] + pi * l['person_stride']:l['person0'] + (pi + 1) * l['person_stride']]
-                pp[l['local_xy']:l['local_xy'] + 2] = cpu(pd['traj_local_xy'])
-                pp[l['local_heading']] = cpu(pd['traj_local_heading'])[0]
-                pp[l['local_dxy']:l['local_dxy'] + 2 * T].view(T, 2)[1:n] = cpu(pd['traj_local_dxy'])
-                pp[l['local_dheading']:l['local_dheading'] + T][1:n] = cpu(pd['traj_local_dheading'])
-                pp[l['local_z']:l['local_z'] + T][:n] = cpu(pd['traj_local_z'])
-                pp[l['local_rot']:l['local_rot'] + 6 * T].view(T, 6)[:n] = cpu(pd['traj_local_rot'])
-                if 'world_dheading' in pd:
-                    pp[l['world_dheading']:l['world_dheading'] + T][:Ts] = cpu(pd['world_dheading'])[:, 0]
+                for name in PERSON_VARS:
+                    if name != 'world_dheading' or name in pd:
+                        person_view(prm, l, pi, name)[var_rows(name, n, Ts)] = cpu(pd[name])
             if P > 1 and d.get('rel_transform_cam'):
                 for (i, j), M in d['rel_transform_cam'].items():
                     t['rel_transform_cam'][si, i, j, :Ts] = cpu(M)[:, :3, :].reshape(Ts, 12).float()
-        if all('root_trans_cam' in pd for d in datas for pd in d['person_data'].values()):
-            rtc = f32(S * P, T, 3)
-            for si, d in enumerate(datas):
-                for pi, idx in enumerate(self.person_ids[si]):
-                    rtc[si * P + pi, :int(d['seq_len'])] = cpu(d['person_data'][idx]['root_trans_cam']).float()
+        if rtc is not None:
             self.root_trans_cam = rtc.to(device)
         jl_host = t.pop('j_local')
         self.t = {k: v.contiguous().to(device) for k, v in t.items()}
         first_jl = j_locals[0][self.person_ids[0][0]]
-        if torch.is_tensor(first_jl) and first_jl.device == torch.device(device) and first_jl.device.type != 'cpu':
-            jl_dev = torch.zeros(jl_host.shape, dtype=torch.float32, device=device)      # device-to-device copies only
-            for si, d in enumerate(datas):
-                for pi, idx in enumerate(self.person_ids[si]):
-                    jl_dev[si * P + pi, :int(d['seq_len'])] = j_locals[si][idx]
-            self.t['j_local'] = jl_dev
-        else:
-            for si, d in enumerate(datas):
-                for pi, idx in enumerate(self.person_ids[si]):
-                    jl_host[si * P + pi, :int(d['seq_len'])] = cpu(j_locals[si][idx]).float()
-            self.t['j_local'] = jl_host.contiguous().to(device)
+        on_device = torch.is_tensor(first_jl) and first_jl.device == torch.device(device) and first_jl.device.type != 'cpu'
+        jl = torch.zeros(jl_host.shape, dtype=torch.float32, device=device) if on_device else jl_host      # (on the device: device-to-device copies only)
+        for si, d in enumerate(datas):
+            for pi, idx in enumerate(self.person_ids[si]):
+                jl[si * P + pi, :int(d['seq_len'])] = j_locals[si][idx] if on_device else cpu(j_locals[si][idx]).float()
+        self.t['j_local'] = jl if on_device else jl.contiguous().to(device)
         self.has_world_dheading = any('world_dheading' in pd for d in datas for pd in d['person_data'].values())
 
     def struct(self):
@@ -340,8 +399,7 @@ class PackedScenes:
         return sb
 
     def person_params(self, si, pi):
-        l = self.layout
-        return self.t['params'][si, l['person0'] + pi * l['person_stride']:l['person0'] + (pi + 1) * l['person_stride']]
+        return person_view(self.t['params'][si], self.layout, pi)
 
     def set_cam_pose(self, cam_poses):
         """cam_poses: list (per scene) of (T,4,4) world->camera arrays."""
@@ -358,7 +416,7 @@ class PackedScenes:
     def unpack_into(self, datas, stage_specs, model_specs, as_torch=True):
         """Writes optimised variables and the outputs of the last forward pass back into the `data` dictionaries, with the
         tensor names the reference uses (global_recon_model.py:396-426,459-480,512-528,598-606)."""
-        l, T, P = self.layout, self.T, self.P
+        l, P = self.layout, self.P
         h = self.fetch()
         conv = (lambda a: torch.from_numpy(np.ascontiguousarray(a))) if as_torch else (lambda a: np.ascontiguousarray(a))
         var = set(stage_specs['opt_variables']) if stage_specs is not None else set()
@@ -373,31 +431,19 @@ class PackedScenes:
             inv[:, 3, 3] = 1.0
             d['cam_pose'], d['cam_pose_inv'] = conv(cam), conv(inv)
             prm = h['params'][si]
-            if 'cam' in var:
-                r6 = prm[l['cam_rot6d']:l['cam_rot6d'] + 6 * T].reshape(T, 6)
-                tr = prm[l['cam_trans']:l['cam_trans'] + 3 * T].reshape(T, 3)
-                if model_specs.get('flag_fixed_cam', False):
-                    d['cam_rot_6d_fix'], d['cam_trans_fix'] = conv(r6[:1]), conv(tr[:1])
-                else:
-                    d['cam_rot_6d'], d['cam_trans'] = conv(r6[:Ts]), conv(tr[:Ts])
             # the residual tensors live in `data` from init_data on (:171-177) whatever the stages optimise: always written back, so a
             # later optimize(continue_opt=True) restarts from them (the device path's _materialise does the same)
             empty = np.where(np.asarray(d['fr_num_persons']) == 0)[0]
-            d['cam_inv_rot_residual'] = conv(prm[l['cam_inv_rot_res']:l['cam_inv_rot_res'] + 6 * T].reshape(T, 6)[empty])
-            d['cam_inv_trans_residual'] = conv(prm[l['cam_inv_trans_res']:l['cam_inv_trans_res'] + 3 * T].reshape(T, 3)[:Ts])
+            cam_vars = () if 'cam' not in var else ('cam_rot_6d_fix', 'cam_trans_fix') if model_specs.get('flag_fixed_cam', False) else ('cam_rot_6d', 'cam_trans')
+            for name in cam_vars + ('cam_inv_rot_residual', 'cam_inv_trans_residual'):
+                d[name] = conv(scene_view(prm, l, name)[var_rows(name, Ts=Ts, empty=empty)])
             for pi, idx in enumerate(self.person_ids[si]):
                 pd = d['person_data'][idx]
                 slot = si * P + pi
                 n = int(pd['fr_end']) - int(pd['fr_start'])
-                pp = prm[l['person0'] + pi * l['person_stride']:l['person0'] + (pi + 1) * l['person_stride']]
-                pd['traj_local_xy'] = conv(pp[l['local_xy']:l['local_xy'] + 2])
-                pd['traj_local_heading'] = conv(pp[l['local_heading']:l['local_heading'] + 1])
-                pd['traj_local_dxy'] = conv(pp[l['local_dxy']:l['local_dxy'] + 2 * T].reshape(T, 2)[1:n])
-                pd['traj_local_dheading'] = conv(pp[l['local_dheading']:l['local_dheading'] + T][1:n])
-                pd['traj_local_z'] = conv(pp[l['local_z']:l['local_z'] + T][:n])
-                pd['traj_local_rot'] = conv(pp[l['local_rot']:l['local_rot'] + 6 * T].reshape(T, 6)[:n])
-                if 'world_dheading' in var or 'world_dheading' in pd:
-                    pd['world_dheading'] = conv(pp[l['world_dheading']:l['world_dheading'] + T][:Ts, None])
+                for name in PERSON_VARS:
+                    if name != 'world_dheading' or name in var or name in pd:
+                        pd[name] = conv(person_view(prm, l, pi, name)[var_rows(name, n, Ts)])
                 pd['smpl_orient_world'] = conv(h['orient_world'][slot, :Ts])
                 pd['root_trans_world'] = conv(h['trans_world'][slot, :Ts])
                 pd['kp_2d_pred'] = conv(h['kp_2d_pred'][slot, :Ts])

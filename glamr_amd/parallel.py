@@ -8,6 +8,7 @@ import torch
 import torch.distributed as dist
 
 # the device entry points of the stepwise core (PersonShardedSchedule tells them from injected ones with `is`)
+from .global_recon import packing, stepwise
 from .global_recon.stepwise import adam_step as _device_adam_step, run_stage as _device_run_stage
 
 
@@ -146,6 +147,8 @@ class PersonShardedSchedule:
         self.collective_seconds = 0.0
         self.launches = 0
         self._side_stream = None                  # the stream the iteration graphs are captured on (made at the first capture)
+        self.iteration_graphs = 0                 # stages whose middle iterations ran as replays of a captured graph
+        self.replay_events = []                   # per such stage (event before, event after, replays): their device time (bench.py)
 
     def owned(self, n_persons):
         lo, hi = shard_range(n_persons, self.rank, self.world)
@@ -183,7 +186,6 @@ class PersonShardedSchedule:
     def run(self, packed, opt_stage_specs, model_specs, max_iters=None, has_wd=False):
         """Runs the whole schedule on `packed` (the FULL scene batch, identical on every rank when the call starts).  On return every rank
         holds the full result: parameters, world poses and projections of all persons, the camera."""
-        from .global_recon import packing, stepwise
         S, P, T, l = packed.S, packed.P, packed.T, packed.layout
         if P < self.world:
             raise ValueError('%d persons cannot be sharded over %d ranks' % (P, self.world))
@@ -193,7 +195,7 @@ class PersonShardedSchedule:
         frozen[:, own] = 0
         packed.t['frozen'] = frozen.reshape(-1).to(packed.device)
         params = packed.t['params']
-        person_cols = [slice(l['person0'] + pi * l['person_stride'], l['person0'] + (pi + 1) * l['person_stride']) for pi in range(P)]
+        person_cols = [packing.person_cols(l, pi) for pi in range(P)]
         for stage, spec in opt_stage_specs.items():
             if model_specs.get('flag_opt_cam_from_person_pose', False) and 'cam' not in spec['opt_variables']:
                 raise NotImplementedError('stage %r derives the camera from the persons: not covered by the person-sharded exchange' % stage)
@@ -225,9 +227,9 @@ class PersonShardedSchedule:
                     grads = self.run_stage(packed, gd, True)                         # 3.
                 self.launches += 2
                 if self.use_dist:
-                    cam = grads[:, :l['person0']].contiguous()
+                    cam = packing.scene_view(grads, l).contiguous()
                     self._all_reduce(cam)                                            # 4.
-                    grads[:, :l['person0']] = cam
+                    packing.scene_view(grads, l).copy_(cam)
                 for pi in not_own:
                     grads[:, person_cols[pi]] = 0.0
                 if self.grad_hook is not None:
@@ -256,14 +258,12 @@ class PersonShardedSchedule:
         initialises the camera parameters and every lazily built table; RCCL communicators must exist before a capture).  Returns True when the
         whole stage has run; None = not applicable (injected run_stage / adam_step, CPU tensors, GLAMR_SHARDED_GRAPH=0) or the capture failed, in
         which case nothing of the stage has run and the caller's plain loop takes over."""
-        import os
         # With more than one rank the captured iteration (collectives inside a HIP graph) is OPT-IN (GLAMR_SHARDED_GRAPH=1): it has only ever run
         # on a process group of one rank -- no multi-GPU box was available to this project -- and a capture that fails on one rank alone would
         # leave the ranks in different collective sequences (a hang, not an error).  The plain loop is what the world_size-2 tests cover.
         knob = os.environ.get('GLAMR_SHARDED_GRAPH', '1' if self.world <= 1 else '0')
         if self.run_stage is not _device_run_stage or self.adam_step is not _device_adam_step or not params.is_cuda or knob == '0':
             return None
-        from .global_recon import stepwise
         adam = stepwise.IndexedAdam(lr, n, params.device)
         adam_indexed = lambda g: adam.step(params, m, v, g)
         snapshot = (params.clone(), m.clone(), v.clone(), self.launches)
@@ -282,9 +282,9 @@ class PersonShardedSchedule:
                 g.replay()
                 self.launches += 2
             ev1.record()
-            self.__dict__.setdefault('replay_events', []).append((ev0, ev1, n - 3))      # (device time of the replayed iterations: bench.py)
+            self.replay_events.append((ev0, ev1, n - 3))
             iteration(n - 1, adam_indexed, report=True)                             # the stage's last iteration, plainly: its evaluation reports
-            self.iteration_graphs = getattr(self, 'iteration_graphs', 0) + 1
+            self.iteration_graphs += 1
             return True
         except Exception as e:      # noqa: BLE001 -- anything (a runtime without capturable collectives, ...): restore and let the plain loop run
             import sys

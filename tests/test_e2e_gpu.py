@@ -511,6 +511,35 @@ def test_ragged_batch_equals_single_runs(make_model):
             assert a['smpl_pose'].shape == (T, 69)
 
 
+def test_lazy_and_eager_unpacking_agree(make_model):
+    """collect() of a batch initialised on the device cuts its dictionaries lazily (_materialise); PackedScenes.unpack_into writes them
+    eagerly.  Both read the params row through packing's one description of it: every key both produce is equal, on a batch with a padding
+    slot, a person that starts after frame 0 and a scene shorter than the batch (what the variables' row ranges depend on)."""
+    md = synth.make_smpl_model()
+    in_dicts = [_trim_person(synth.make_in_dict(seed=31, num_frames=24, num_persons=2, smpl_model=md), 1, 3, 20),
+                synth.make_in_dict(seed=32, num_frames=17, num_persons=1, smpl_model=md)]
+    model = make_model('glamr_dynamic_multi')
+    datas, packed = model.init_data_batch(in_dicts, [mg.latents_for(d, s) for d, s in zip(in_dicts, (31, 32))])
+    model.run_schedule(packed, 1)
+    lazy = model.collect(datas, packed)
+    assert (packed.S, packed.P, packed.T) == (2, 2, 24) and int(lazy[0]['person_data'][1]['fr_start']) == 3 and lazy[1]['seq_len'] == 17
+    eager = [dict(seq_len=d['seq_len'], fr_num_persons=np.asarray(d['fr_num_persons']),
+                  person_data={i: dict(fr_start=pd['fr_start'], fr_end=pd['fr_end']) for i, pd in d['person_data'].items()}) for d in lazy]
+    packed.unpack_into(eager, {'opt_variables': model._all_vars()}, model.specs, as_torch=False)
+    n_compared = 0
+    for a, b in zip(lazy, eager):
+        pairs = [(a, b, 'scene')] + [(a['person_data'][i], b['person_data'][i], 'person %r' % i) for i in b['person_data']]
+        for x, y, who in pairs:
+            common = [k for k in y if k in x and isinstance(y[k], np.ndarray)]
+            assert {'traj_local_rot', 'traj_local_dxy', 'world_dheading', 'kp_2d_pred'} <= set(common) or \
+                {'cam_rot_6d', 'cam_trans', 'cam_inv_rot_residual', 'cam_inv_trans_residual', 'cam_pose', 'cam_pose_inv'} <= set(common), (who, common)
+            for k in common:
+                xa = np.asarray(x[k])
+                assert xa.shape == y[k].shape and np.array_equal(xa, y[k]), (who, k)
+                n_compared += 1
+    assert n_compared == 2 * 7 + 3 * 11      # per scene: the six above and fr_num_persons; per person: seven variables and four outputs
+
+
 def test_stream_of_batches_equals_batch_calls(make_model):
     """optimize_stream (the host-side software pipeline: pinned staging + uploads of batch i + 1 and output dictionaries of batch i - 1
     under the device work of batch i) returns, batch by batch and key by key, what optimize_batch returns for the same batches."""

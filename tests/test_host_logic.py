@@ -45,7 +45,7 @@ def test_person_preprocessing_is_bit_exact(golden, cfg_id, T, P, K):
     g = golden('grecon_%s_T%d_P%d' % (cfg_id, T, P))
     in_dict = synth.make_in_dict(seed=3, num_frames=T, num_persons=P, smpl_model=synth.make_smpl_model())
     opt = GlobalReconOptimizer.__new__(GlobalReconOptimizer)       # host logic only: no device, no library
-    opt.flag_filter_pose = True
+    opt.flag_filter_pose, opt.flag_make_invis_with_keypoint = True, False
     for pi in range(P):
         d = opt._person_arrays(in_dict['est'][pi])
         for key in ('visible', 'visible_orig', 'exist_frames', 'vis_frames', 'invis_frames', 'kp_2d_score', 'kp_2d_aligned', 'cam_K'):
@@ -248,3 +248,165 @@ def test_stage_iters_and_end_stage():
         assert torch.equal(packed.t['cam_pose'], want)
     assert seen == [False, True, True]
     assert stepwise.end_stage(packed, spec, True) is True
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# the params row: packing's description of it (PERSON_VARS / SCENE_VARS, person_view / scene_view) against explicit offsets
+# ------------------------------------------------------------------------------------------------------------------------------------
+_PERSON_NAMES = ('traj_local_xy', 'traj_local_heading', 'traj_local_dxy', 'traj_local_dheading', 'traj_local_z', 'traj_local_rot', 'world_dheading')
+
+
+def _packable_scenes():
+    """Two scenes of 7 and 5 frames.  Scene 0: persons 0 on [0, 7) and 3 on [2, 6), nobody seen in frame 1 (a row of cam_inv_rot_residual);
+    scene 1: one person, so its second slot is padding.  Every packed variable holds distinct non-zero numbers."""
+    counter = [0]
+
+    def fill(*shape):
+        n = int(np.prod(shape))
+        counter[0] += n
+        return (np.arange(counter[0] - n, counter[0], dtype=np.float32) + 1.0).reshape(shape)
+
+    def person(Ts, fs, fe, vis):
+        n = fe - fs
+        eye = np.tile(np.eye(4, dtype=np.float32), (Ts, 1, 1))
+        return {'fr_start': fs, 'fr_end': fe, 'vis_frames': vis, 'kp_2d_aligned': np.zeros((Ts, 26, 2)), 'kp_2d_score': np.zeros((Ts, 26)),
+                'cam_K': eye[:, :3, :3].copy(), 'traj_local_pred': np.zeros((n, 11), np.float32), 'smpl_orient_cam': np.zeros((Ts, 3), np.float32),
+                'smpl_orient_world_base': np.zeros((Ts, 3), np.float32), 'root_trans_world_base': np.zeros((Ts, 3), np.float32), 'person2cam': eye,
+                'traj_local_xy': fill(2), 'traj_local_heading': fill(1), 'traj_local_dxy': fill(n - 1, 2), 'traj_local_dheading': fill(n - 1),
+                'traj_local_z': fill(n), 'traj_local_rot': fill(n, 6), 'world_dheading': fill(Ts, 1)}
+
+    def scene(name, Ts, persons):
+        fr_num = sum(pd['vis_frames'].astype(np.int64) for pd in persons.values())
+        return {'seq_name': name, 'seq_len': Ts, 'person_data': persons, 'fr_num_persons': fr_num, 'cam_pose': np.tile(np.eye(4, dtype=np.float32), (Ts, 1, 1)),
+                'cam_inv_rot_residual': fill(int((fr_num == 0).sum()), 6), 'cam_inv_trans_residual': fill(Ts, 3)}
+    v0 = np.ones(7, bool)
+    v0[1] = False
+    v3 = np.zeros(7, bool)
+    v3[2:6] = True
+    v3[1] = False
+    datas = [scene('a', 7, {0: person(7, 0, 7, v0), 3: person(7, 2, 6, v3)}), scene('b', 5, {0: person(5, 0, 5, np.ones(5, bool))})]
+    j_locals = [{idx: torch.zeros((d['seq_len'], 26, 3)) for idx in d['person_data']} for d in datas]
+    return datas, j_locals
+
+
+def _expected_params(datas, l, P, T):
+    """The params array PackedScenes builds from `datas`, by explicit offsets into param_layout_py's dictionary."""
+    want = np.zeros((len(datas), l['scene_stride']), np.float32)
+    for si, d in enumerate(datas):
+        Ts, row = d['seq_len'], want[si]
+        for f, r in zip(np.where(d['fr_num_persons'] == 0)[0], d['cam_inv_rot_residual']):
+            row[l['cam_inv_rot_res'] + 6 * f:l['cam_inv_rot_res'] + 6 * f + 6] = r
+        row[l['cam_inv_trans_res']:l['cam_inv_trans_res'] + 3 * Ts] = d['cam_inv_trans_residual'].reshape(-1)
+        for pi, pd in enumerate(d['person_data'].values()):
+            b, n = l['person0'] + pi * l['person_stride'], pd['fr_end'] - pd['fr_start']
+            row[b + l['local_xy']:b + l['local_xy'] + 2] = pd['traj_local_xy']
+            row[b + l['local_heading']] = pd['traj_local_heading'][0]
+            row[b + l['local_dxy'] + 2:b + l['local_dxy'] + 2 * n] = pd['traj_local_dxy'].reshape(-1)
+            row[b + l['local_dheading'] + 1:b + l['local_dheading'] + n] = pd['traj_local_dheading']
+            row[b + l['local_z']:b + l['local_z'] + n] = pd['traj_local_z']
+            row[b + l['local_rot']:b + l['local_rot'] + 6 * n] = pd['traj_local_rot'].reshape(-1)
+            row[b + l['world_dheading']:b + l['world_dheading'] + Ts] = pd['world_dheading'][:, 0]
+    return want
+
+
+@pytest.mark.parametrize('fixed_cam', [False, True])
+def test_pack_unpack_round_trip_and_the_row_by_explicit_offsets(fixed_cam):
+    from glamr_amd.global_recon import packing
+    datas, j_locals = _packable_scenes()
+    assert (datas[0]['fr_num_persons'] == 0).sum() == 1 and datas[0]['cam_inv_rot_residual'].shape == (1, 6)
+    packed = packing.PackedScenes(datas, j_locals, 'cpu')
+    S, P, T, l = packed.S, packed.P, packed.T, packed.layout
+    assert (S, P, T) == (2, 2, 7) and l == packing.param_layout_py(2, 7)
+    want = _expected_params(datas, l, P, T)
+    assert np.array_equal(packed.t['params'].numpy(), want)
+    assert not want[1, l['person0'] + l['person_stride']:].any() and not want[1, :l['person0']][15 * T + 3 * 5:].any()      # the padding slot, the frames past Ts
+    # the camera variables are the kernel's to write: distinct numbers in their columns, to be found again in the dictionaries
+    cam = packed.t['params'].numpy()[:, :l['cam_inv_rot_res']]
+    cam[...] = 1e4 + np.arange(cam.size, dtype=np.float32).reshape(cam.shape)
+    copies = [dict(seq_len=d['seq_len'], fr_num_persons=d['fr_num_persons'],
+                   person_data={i: dict(fr_start=pd['fr_start'], fr_end=pd['fr_end']) for i, pd in d['person_data'].items()}) for d in datas]
+    packed.unpack_into(copies, {'opt_variables': list(packing.VAR_BITS)}, {'flag_fixed_cam': fixed_cam}, as_torch=False)
+    for si, (d, c) in enumerate(zip(datas, copies)):
+        Ts = d['seq_len']
+        for name in ('cam_inv_rot_residual', 'cam_inv_trans_residual'):
+            assert c[name].dtype == np.float32 and np.array_equal(c[name], d[name]), name
+        r6, tr = cam[si, :6 * T].reshape(T, 6), cam[si, 6 * T:9 * T].reshape(T, 3)
+        if fixed_cam:
+            assert np.array_equal(c['cam_rot_6d_fix'], r6[:1]) and np.array_equal(c['cam_trans_fix'], tr[:1]) and 'cam_rot_6d' not in c
+        else:
+            assert np.array_equal(c['cam_rot_6d'], r6[:Ts]) and np.array_equal(c['cam_trans'], tr[:Ts]) and 'cam_rot_6d_fix' not in c
+        for idx, pd in d['person_data'].items():
+            for name in _PERSON_NAMES:
+                got = c['person_data'][idx][name]
+                assert got.shape == pd[name].shape and np.array_equal(got, pd[name]), (si, idx, name)
+
+
+@pytest.mark.parametrize('kind', ['numpy', 'torch'])
+def test_params_views_cut_the_last_axis_of_a_whole_batch(kind):
+    """person_view / scene_view on the (S, scene_stride) array: views with the leading S; writing the (S, T, 6) traj_local_rot view of person 1
+    changes exactly person_params(si, 1)[local_rot : local_rot + 6 T] and nothing else."""
+    from glamr_amd.global_recon import packing
+    S, P, T = 3, 2, 5
+    packed = packing.PackedScenes.empty(S, P, T, torch.device('cpu'))
+    l, params = packed.layout, packed.t['params']
+    arr = params.numpy() if kind == 'numpy' else params
+    rot = packing.person_view(arr, l, 1, 'traj_local_rot')
+    assert tuple(rot.shape) == (S, T, 6)
+    values = np.arange(1, S * T * 6 + 1, dtype=np.float32).reshape(S, T, 6)
+    rot[...] = values if kind == 'numpy' else torch.from_numpy(values)
+    want = np.zeros((S, l['scene_stride']), np.float32)
+    for si in range(S):
+        b = l['person0'] + l['person_stride'] + l['local_rot']
+        want[si, b:b + 6 * T] = values[si].reshape(-1)
+        assert np.array_equal(packed.person_params(si, 1)[l['local_rot']:l['local_rot'] + 6 * T].numpy(), values[si].reshape(-1))
+    assert np.array_equal(params.numpy(), want)
+    assert tuple(packing.person_view(arr, l, 0).shape) == (S, l['person_stride']) and tuple(packing.scene_view(arr, l).shape) == (S, l['person0'])
+    assert tuple(packing.scene_view(arr, l, 'cam_trans').shape) == (S, T, 3) and tuple(packing.person_view(arr[0], l, 1, 'traj_local_xy').shape) == (2,)
+    assert tuple(packing.person_view(arr, l, 0, 'world_dheading').shape) == (S, T, 1) and packing.person_cols(l, 1) == slice(l['person0'] + l['person_stride'], l['scene_stride'])
+
+
+def test_off_kernel_terms_are_split_once():
+    """packing.split_off_kernel: what GlobalReconOptimizer.__init__ takes off the stages' loss_cfg for the launch-by-launch schedule."""
+    import copy
+    from glamr_amd.global_recon import packing
+    from glamr_amd.global_recon.configs import CONFIGS, get_config
+    for cfg_id in CONFIGS:
+        specs = get_config(cfg_id)['opt_stage_specs']
+        rest, pen, aux = packing.split_off_kernel(specs)
+        assert rest is specs and pen == {} and aux == {}, cfg_id
+    specs = get_config('glamr_dynamic_multi')['opt_stage_specs']
+    specs['init_opt']['loss_cfg']['cam_traj_trans'] = {'weight': 2, 'first_frame_weight': 5}
+    specs['main_opt']['loss_cfg']['penetration'] = {'weight': 3}
+    specs['main_opt']['loss_cfg']['cam_rot_smoothness'] = {'weight': 0.5, 'monitor_only': True}
+    specs['main_opt']['loss_cfg']['local_traj_dheading_reg'] = {'weight': 7.0}
+    before = copy.deepcopy(specs)
+    rest, pen, aux = packing.split_off_kernel(specs)
+    assert specs == before and rest is not specs
+    assert pen == {'main_opt': {'weight': 3.0, 'monitor_only': False}}
+    assert aux == {'init_opt': {'cam_traj_trans': {'weight': 2.0, 'monitor_only': False, 'first_frame_weight': 5.0}},
+                   'main_opt': {'cam_rot_smoothness': {'weight': 0.5, 'monitor_only': True}, 'local_traj_dheading_reg': {'weight': 7.0, 'monitor_only': False}}}
+    plain = get_config('glamr_dynamic_multi')['opt_stage_specs']
+    assert rest == plain and list(rest) == list(plain) and all(list(rest[s]['loss_cfg']) == list(plain[s]['loss_cfg']) for s in plain)
+    specs['main_opt']['loss_cfg']['cam_depth_smoothness'] = {'weight': 1.0, 'rot_type': 'quat'}
+    with pytest.raises(NotImplementedError, match='cam_depth_smoothness'):
+        packing.split_off_kernel(specs)
+
+
+def test_the_name_a_refusal_gives_an_off_kernel_term():
+    """GlobalReconOptimizer._off_kernel_term for the seven combinations of {extra_loss, penetration, terms of AUX_LOSS_IDS}: the caller's term
+    before the penetration term before the others (what ExtraLossSchedule.run names), None without any."""
+    from glamr_amd.global_recon.models.global_recon_model import GlobalReconOptimizer
+    pen = {'main_opt': {'weight': 1.0, 'monitor_only': False}}
+    aux = {'init_opt': {'cam_traj_trans': {'weight': 1.0, 'monitor_only': False}},
+           'main_opt': {'local_traj_dheading_reg': {'weight': 1.0, 'monitor_only': False}, 'cam_rot_smoothness': {'weight': 1.0, 'monitor_only': True}}}
+    aux_name = 'the loss_cfg terms cam_rot_smoothness, cam_traj_trans, local_traj_dheading_reg'
+    want = {(True, False, False): 'extra_loss', (True, True, False): 'extra_loss', (True, False, True): 'extra_loss', (True, True, True): 'extra_loss',
+            (False, True, False): 'the penetration term (loss_cfg)', (False, True, True): 'the penetration term (loss_cfg)', (False, False, True): aux_name}
+    opt = GlobalReconOptimizer.__new__(GlobalReconOptimizer)
+    for (has_fn, has_pen, has_aux), name in want.items():
+        opt._extra_loss, opt._pen_cfg, opt._aux_cfg = (lambda ctx: None) if has_fn else None, pen if has_pen else {}, aux if has_aux else {}
+        assert opt._off_kernel_term() == name, (has_fn, has_pen, has_aux)
+    opt._extra_loss, opt._pen_cfg, opt._aux_cfg = None, {}, {'main_opt': {'cam_depth_smoothness': {'weight': 1.0, 'monitor_only': False}}}
+    assert opt._off_kernel_term() == 'the loss_cfg term cam_depth_smoothness'
+    opt._aux_cfg = {}
+    assert opt._off_kernel_term() is None

@@ -36,7 +36,7 @@ for k in range(NB):
     cs.wait_event(rin.upload_done)
     with torch.cuda.stream(cs):
         e0 = torch.cuda.Event(enable_timing=True); e0.record()
-        datas, packed = m._resident_for_stream(rin, None)
+        datas, packed = m.optimize_resident(rin, None)
         e1 = torch.cuda.Event(enable_timing=True); e1.record()
         done = torch.cuda.Event(); done.record()
     log.append(('enqueue', k, t_e0, now()))
