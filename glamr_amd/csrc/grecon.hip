@@ -6,7 +6,7 @@
 // one per CU (blockIdx -> scene; with >= 256 scenes every CU is busy; XCD placement is irrelevant because scenes never
 // communicate).
 #include "common.hpp"
-#include "grecon_algo.hpp"
+#include "grecon_launch.hpp"
 #include "block_rt.hpp"
 #include <map>
 #include <memory>
@@ -19,15 +19,8 @@
 namespace glamr {
 namespace GLAMR_GRECON_NS {
 
-constexpr int MAX_THREADS = 512;
 static_assert(MAX_THREADS <= 512, "DeviceRT::scan_multi / scan_regs fetch the wave totals of a workgroup as two float4 reads: at most 8 waves (block_rt.hpp)");
-constexpr int WAVES_PER_EU = 2;
-// the largest on-chip arena a stage launch asks for
-#ifdef GLAMR_GRECON_WIDE
-constexpr size_t LDS_MAX = 96 * 1024;      // (the description of 32 persons takes ~25 KB of static LDS)
-#else
-constexpr size_t LDS_MAX = 153 * 1024;
-#endif
+static_assert(STAGE_RED_FLOATS == RT_RED_FLOATS, "grecon_launch.hpp's estimate of the static LDS");
 
 struct KernelArgs {
   glamr_scene_batch b;
@@ -141,6 +134,43 @@ std::shared_ptr<LaunchEvent> new_launch_event() {
 }
 void record_launch(const void* workspace, hipStream_t stream);
 #endif
+// CUs of a device (per device: a process may drive more than one GPU)
+int device_cu_count(int dev) {
+  static std::mutex mu; static std::map<int, int> cus;
+  std::lock_guard<std::mutex> lock(mu);
+  int& n = cus[dev];
+  if (n <= 0 && (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)) n = 256;
+  return n;
+}
+// Adam's step size and second-moment correction per iteration, in the reference's own arithmetic (Python doubles, libm pow): a running product on
+// the device would differ in the last bit of the fp32 scalar now and then, and the update must not (rotmath.hpp).  One table per (device, lr, niters),
+// uploaded the first time a stage with that schedule runs and kept for the life of the process: no per-launch host->device copy (a pageable copy on the launch stream would stall a pipelined host).
+int adam_table(double lr, int niters, const float** out) {
+  static std::mutex mu; static std::map<std::tuple<int, double, int>, float*> tables;
+  int devid = 0;
+  GLAMR_HIP_CHECK(hipGetDevice(&devid));
+  std::lock_guard<std::mutex> lock(mu);
+  float*& dtab = tables[std::make_tuple(devid, lr, niters)];
+  if (!dtab) {
+    std::vector<float> tab(2 * (size_t)niters);
+    for (int i = 0; i < niters; ++i) adam_coef_host(lr, i + 1, &tab[2 * (size_t)i]);
+    GLAMR_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dtab), tab.size() * sizeof(float)));
+    GLAMR_HIP_CHECK(hipMemcpy(dtab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+  }
+  *out = dtab;
+  return GLAMR_OK;
+}
+// launches the plan's instance; its dynamic-LDS limit is raised once per (device, instance) and process (a driver call per launch is host time on every step)
+int launch_stage(void (*kern)(KernelArgs), const StagePlan& plan, int dev, hipStream_t stream, const KernelArgs& ka) {
+  if (plan.lds_bytes) {
+    static std::mutex mu; static std::set<std::pair<int, const void*>> raised;
+    std::lock_guard<std::mutex> lock(mu);
+    if (raised.insert(std::make_pair(dev, reinterpret_cast<const void*>(kern))).second)
+      GLAMR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX));
+  }
+  hipLaunchKernelGGL(kern, dim3(ka.b.n_scenes), dim3(plan.threads), plan.lds_bytes, stream, ka);
+  return GLAMR_OK;
+}
 int current_device() {
   int dev = 0;
   return hipGetDevice(&dev) == hipSuccess ? dev : 0;
@@ -194,134 +224,22 @@ extern "C" int glamr_grecon_run_stage(const glamr_scene_batch* batch, const glam
   GLAMR_HIP_CHECK(hipMemsetAsync(workspace, 0xFF, 8, stream));
   GLAMR_HIP_CHECK(hipMemsetAsync(static_cast<char*>(workspace) + 8, 0, 8, stream));
   ka.workspace = reinterpret_cast<float*>(static_cast<char*>(workspace) + GLAMR_GRECON_WS_HEADER);
-  // Adam's step size and second-moment correction per iteration, in the reference's own arithmetic (Python doubles, libm pow): a
-  // running product on the device would differ in the last bit of the fp32 scalar now and then, and the update must not (rotmath.hpp).
-  // One table per (device, lr, niters), uploaded the first time a stage with that schedule runs and kept for the life of the process:
-  // no per-launch host->device copy (a pageable copy on the launch stream would stall a pipelined host).
   ka.adam_tab = nullptr;
-  if (stage->niters > 0 && stage->niters <= ADAM_TAB_MAX) {
-    static std::mutex mu;
-    static std::map<std::tuple<int, double, int>, float*> tables;
-    int devid = 0;
-    GLAMR_HIP_CHECK(hipGetDevice(&devid));
-    std::lock_guard<std::mutex> lock(mu);
-    float*& dtab = tables[std::make_tuple(devid, stage->lr, (int)stage->niters)];
-    if (!dtab) {
-      std::vector<float> tab(2 * (size_t)stage->niters);
-      for (int i = 0; i < stage->niters; ++i) adam_coef_host(stage->lr, i + 1, &tab[2 * (size_t)i]);
-      GLAMR_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dtab), tab.size() * sizeof(float)));
-      GLAMR_HIP_CHECK(hipMemcpy(dtab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    ka.adam_tab = dtab;
-  }
+  if (stage->niters > 0 && stage->niters <= ADAM_TAB_MAX && adam_table(stage->lr, (int)stage->niters, &ka.adam_tab) != GLAMR_OK) return GLAMR_E_HIP;
   ka.ws_floats_per_scene = align_up(scene_workspace_floats(batch->max_persons, layout_frames(batch->max_persons, batch->max_len)), 64);
   ka.grads_out = grads_out;
-  int threads = (batch->max_len + 63) / 64 * 64;
-  if (threads > MAX_THREADS) threads = MAX_THREADS;
-  // on-chip arena: prefix-sum / neighbour-exchange arrays first, then as much of the compact keypoint table as fits
-  size_t LDS_BUDGET = LDS_MAX;
-  // Occupancy: a workgroup's waves hold 256 registers each, so a CU (4 SIMDs x 512 registers) takes 8 / waves workgroups -- if their arenas fit its
-  // 160 KB together.  When the batch has more scenes than the chip has CUs, the arena is capped at that share (the keypoint table
-  // overflows into the workspace): 1024 scenes of 256 frames 40.1 -> 27.5 ms per 500 iterations.  A 300-frame scene has 5 waves: one per CU.
-  const int devid_launch = current_device();
-  const int n_cus = [devid_launch] {      // per device: a process may drive more than one GPU
-    static std::mutex cmu;
-    static std::map<int, int> cus;
-    std::lock_guard<std::mutex> lock(cmu);
-    int& n = cus[devid_launch];
-    if (n <= 0 && (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, devid_launch) != hipSuccess || n <= 0)) n = 256;
-    return n;
-  }();
-  const int wgs_per_cu = 4 * WAVES_PER_EU / (threads / 64);
-  // (the exchange arrays alone -- arena mode 3: parameters and Adam moments then stay in the workspace; keeping them on chip as well,
-  // mode 1, needs 113 instead of 53 floats per frame and is what a scene that has its CU to itself gets)
-  const size_t full_arena = scene_fast_floats(batch->max_persons, batch->max_len, 3) * sizeof(float);
-  if (wgs_per_cu > 1 && batch->n_scenes > n_cus) {
-    // static LDS per workgroup: the scene description (8 persons ~4 KB, 32 persons ~25 KB in the wide build), the scan scratch, the
-    // stage descriptor and the layout -- taken from the types, so the share is right for both builds
-    const size_t static_lds = sizeof(Scene) + RT_RED_FLOATS * sizeof(float) + sizeof(glamr_stage_desc) + sizeof(glamr_param_layout) + 256;
-    const size_t share = (size_t)160 * 1024 / wgs_per_cu - static_lds;
-    if (full_arena <= share && batch->max_len <= threads) LDS_BUDGET = share;
-  }
-  if (const char* e = std::getenv("GLAMR_GRECON_LDS_KB_RT")) {      // development aid (tools/overlap_probe.py)
-    const size_t v = (size_t)std::atoi(e) * 1024;
-    LDS_BUDGET = v < 16384 ? (size_t)16384 : (v > LDS_MAX ? LDS_MAX : v);
-  }
-  // constant-layout instance (every array address of the loop a compile-time constant): one person, 257..304 frames, a thread per
-  // frame, the full arena of the 304-frame layout fits, and the caller does not ask for the gradient record
-  const int lay_len = layout_frames(batch->max_persons, batch->max_len);
-  const bool no_const_layout = std::getenv("GLAMR_GRECON_NO_CONST_LAYOUT") != nullptr;      // development aid / A-B tests (read per launch)
-  const bool const_layout = lay_len == GLAMR_CONST_LAYOUT_FRAMES && !grads_out && !no_const_layout && batch->max_len <= threads && !(batch->loss_history && stage->niters > 0) &&
-                            scene_fast_floats(1, lay_len, 1) * sizeof(float) <= LDS_BUDGET;
-  ka.layout_len = const_layout ? lay_len : 0;
-  const int arena_len = const_layout ? lay_len : batch->max_len;
-  const size_t full = scene_fast_floats(batch->max_persons, arena_len, 1) * sizeof(float);
-  const size_t lite = scene_fast_floats(batch->max_persons, batch->max_len, 2) * sizeof(float);
-  // 1 full arena + Adam state of single-person scenes, 3 full arena (both: single-pass instances, a thread per frame), 2 lite arena,
-  // 0 everything in the workspace
-  const bool per_frame = batch->max_len <= threads;
-  // (4 = mid, scenes of several persons only: BASELINE configs[3]'s 4 x 300 frames take 143 of the 153 KB; `GLAMR_GRECON_NO_MID_ARENA` keeps them on the lite arena)
-  const size_t mid = scene_fast_floats(batch->max_persons, batch->max_len, 4) * sizeof(float);
-  const bool no_mid = std::getenv("GLAMR_GRECON_NO_MID_ARENA") != nullptr;      // development aid / A-B tests (read per launch)
-  ka.use_lds = (full <= LDS_BUDGET && per_frame) ? 1 : ((full_arena <= LDS_BUDGET && per_frame) ? 3 : ((mid <= LDS_BUDGET && batch->max_persons > 1 && !no_mid) ? 4 : (lite <= LDS_BUDGET ? 2 : 0)));
-  // a launch that records the per-iteration loss history (glamr_scene_batch.loss_history) runs on the plain instance: the reporting evaluation
-  // every iteration is a diagnostic mode, and the arena instances' loops stay free of it
-  if (batch->loss_history && stage->niters > 0) ka.use_lds = 0;
-  const size_t base = ka.use_lds == 1 ? full : (ka.use_lds == 3 ? full_arena : (ka.use_lds == 4 ? mid : lite));
-  const size_t want = base + (size_t)NJ * 6 * batch->max_persons * arena_len * sizeof(float);
-  const size_t dyn = ka.use_lds ? (want < LDS_BUDGET ? want : LDS_BUDGET) : 0;
-  ka.fast_floats = (unsigned)(dyn / sizeof(float));
-  // SINGLE needs every scene of the batch to hold exactly one person: max_persons == 1 guarantees it
-  [[maybe_unused]] const bool single = batch->max_persons == 1;
-  auto launch = [&](auto kern, size_t lds) -> int {
-    if (lds) {      // once per (device, instance) and process (a driver call per launch is host time on every step)
-      static std::mutex amu;
-      static std::set<std::pair<int, const void*>> raised;
-      std::lock_guard<std::mutex> lock(amu);
-      if (raised.insert(std::make_pair(devid_launch, reinterpret_cast<const void*>(kern))).second)
-        GLAMR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX));
-    }
-    hipLaunchKernelGGL(kern, dim3(batch->n_scenes), dim3(threads), lds, stream, ka);
-    return GLAMR_OK;
-  };
-  int rc;
-  if (batch->g_traj_local) {
-    // the general instance (several persons, any camera mode) on the lite arena, or in the workspace: one pair per compile
-    ka.use_lds = lite <= LDS_BUDGET ? 2 : 0;
-    const size_t want2 = lite + (size_t)NJ * 6 * batch->max_persons * batch->max_len * sizeof(float);
-    ka.fast_floats = (unsigned)((ka.use_lds ? (want2 < LDS_BUDGET ? want2 : LDS_BUDGET) : 0) / sizeof(float));
-    ka.layout_len = 0;
-    rc = ka.use_lds == 2 ? launch(grecon_stage_traj_grad_kernel<2>, (size_t)ka.fast_floats * sizeof(float)) : launch(grecon_stage_traj_grad_kernel<0>, 0);
-  } else {
-#ifdef GLAMR_GRECON_WIDE
-  if (ka.use_lds == 1 || ka.use_lds == 3 || ka.use_lds == 4) {      // (the full arena of > 8 persons never fits; kept from being instantiated -- the mid arena likewise)
-    ka.use_lds = lite <= LDS_BUDGET ? 2 : 0;
-    const size_t want2 = lite + (size_t)NJ * 6 * batch->max_persons * arena_len * sizeof(float);
-    ka.fast_floats = (unsigned)((ka.use_lds ? (want2 < LDS_BUDGET ? want2 : LDS_BUDGET) : 0) / sizeof(float));
-  }
-  const size_t dynw = (size_t)ka.fast_floats * sizeof(float);
-  rc = ka.use_lds == 2 ? launch(grecon_stage_kernel<2, false, 0>, dynw) : launch(grecon_stage_kernel<0, false, 0>, 0);
-#else
-  const int cam = camera_mode(*stage);      // per-camera-mode instances: 24.1 vs 26.1 us per iteration (1 person), 61.8 vs 66.2 (2 persons, main stage)
-  constexpr int CL = GLAMR_CONST_LAYOUT_FRAMES;
-  if (ka.use_lds == 1 && single && const_layout)
-    rc = cam == 1 ? launch(grecon_stage_kernel<1, true, 1, CL>, dyn) : cam == 2 ? launch(grecon_stage_kernel<1, true, 2, CL>, dyn) : launch(grecon_stage_kernel<1, true, 0, CL>, dyn);
-  else if (ka.use_lds == 1 && single)
-    rc = cam == 1 ? launch(grecon_stage_kernel<1, true, 1>, dyn) : cam == 2 ? launch(grecon_stage_kernel<1, true, 2>, dyn) : launch(grecon_stage_kernel<1, true, 0>, dyn);
-  else if (ka.use_lds == 3 && single)
-    rc = cam == 1 ? launch(grecon_stage_kernel<3, true, 1>, dyn) : cam == 2 ? launch(grecon_stage_kernel<3, true, 2>, dyn) : launch(grecon_stage_kernel<3, true, 0>, dyn);
-  else if (ka.use_lds == 1 || ka.use_lds == 3)      // several persons: the two full-arena modes are the same layout
-    rc = cam == 1 ? launch(grecon_stage_kernel<1, false, 1>, dyn) : cam == 2 ? launch(grecon_stage_kernel<1, false, 2>, dyn) : cam == 3 ? launch(grecon_stage_kernel<1, false, 3>, dyn) : launch(grecon_stage_kernel<1, false, 0>, dyn);
-  else if (ka.use_lds == 2 && single)
-    rc = cam == 1 ? launch(grecon_stage_kernel<2, true, 1>, dyn) : cam == 2 ? launch(grecon_stage_kernel<2, true, 2>, dyn) : launch(grecon_stage_kernel<2, true, 0>, dyn);
-  else if (ka.use_lds == 4)
-    rc = cam == 1 ? launch(grecon_stage_kernel<4, false, 1>, dyn) : cam == 2 ? launch(grecon_stage_kernel<4, false, 2>, dyn) : cam == 3 ? launch(grecon_stage_kernel<4, false, 3>, dyn) : launch(grecon_stage_kernel<4, false, 0>, dyn);
-  else if (ka.use_lds == 2)
-    rc = cam == 1 ? launch(grecon_stage_kernel<2, false, 1>, dyn) : cam == 2 ? launch(grecon_stage_kernel<2, false, 2>, dyn) : cam == 3 ? launch(grecon_stage_kernel<2, false, 3>, dyn) : launch(grecon_stage_kernel<2, false, 0>, dyn);
-  else
-    rc = launch(grecon_stage_kernel<0, false, 0>, 0);
-#endif
-  }
+  // which instance, with how many threads and which arena: grecon_launch.hpp
+  const int dev = current_device();
+  const StagePlan plan = plan_stage({batch->n_scenes, batch->max_persons, batch->max_len, (int)stage->niters, camera_mode(*stage), grads_out != nullptr,
+                                     batch->loss_history != nullptr, batch->g_traj_local != nullptr}, launch_env(device_cu_count(dev)));
+  ka.use_lds = plan.use_lds; ka.fast_floats = plan.fast_floats; ka.layout_len = plan.layout_len;
+  int rc = GLAMR_OK;
+  const bool known = with_stage_instance(plan.inst, [&](auto tag) {
+    constexpr StageInstance I = decltype(tag)::value;
+    if constexpr (I.gt) rc = launch_stage(grecon_stage_traj_grad_kernel<I.fast>, plan, dev, stream, ka);
+    else rc = launch_stage(grecon_stage_kernel<I.fast, I.single, I.cam, I.tmc>, plan, dev, stream, ka);
+  });
+  GLAMR_REQUIRE(known, "no stage kernel instance FAST=%d SINGLE=%d CAM=%d TMC=%d GT=%d", plan.inst.fast, plan.inst.single, plan.inst.cam, plan.inst.tmc, plan.inst.gt);
   if (rc) return rc;
   GLAMR_HIP_CHECK(hipGetLastError());
 #ifndef GLAMR_GRECON_WIDE

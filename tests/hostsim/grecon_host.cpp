@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE: instantiates the per-scene optimiser algorithm (glamr_amd/csrc/grecon_algo.hpp) with a single-threaded
 // host runtime so the CPU test-suite can check its gradients and control flow against the oracle without a GPU.
 // Same argument structs as the C ABI, but every pointer is a HOST pointer.  Never loaded by the product.
-#include "../../glamr_amd/csrc/grecon_algo.hpp"
+#include "stage_plan_shim.hpp"      // (grecon_algo.hpp through grecon_launch.hpp, and the plan's own entry points)
 #include <vector>
 using namespace glamr::grecon;
 
@@ -41,33 +41,48 @@ struct TraceRT : HostRT {
 // entry point that takes a stage descriptor refuses it (return code 2; the callers assert 0)
 static bool unsupported(const glamr_stage_desc* st) { return (st->flags & GLAMR_FLAG_ABSOLUTE_HEADING) != 0; }
 
+// Instances are chosen through the device launcher's list (grecon_launch.hpp: with_stage_instance), and this one: the single-person / camera-mode
+// specialisations WITHOUT an arena (FAST = 0), which the device never launches and this runtime -- no arena unless an entry point lends one -- does.
+using HostOnlyInstances = InstanceList<Inst<0, true, 1>, Inst<0, true, 2>, Inst<0, true, 0>, Inst<0, false, 1>, Inst<0, false, 2>, Inst<0, false, 3>>;
+
+// One stage over the first `n_scenes` scenes of the batch, each on the specialisation <fast, ., ., tmc> for its own person count and the stage's
+// camera mode (gt: on the instance that also writes dL/d traj_local_pred): the workspace, the Adam table and, for fast = 1 -- the full arena of
+// single-person scenes -- the arena in host memory with room for two keypoint rows "on chip"; tmc > 0 = arena / workspace laid out for that many
+// frames (the constant-layout instance).  -3: an instance neither list has, or an arena mode nobody lends this runtime an arena for.
 template <class RT>
-static void run_one(RT& rt, const glamr_scene_batch* b, const glamr_stage_desc* st, const glamr_param_layout& l, Scene& sc, int si) {
+static int run_scenes(RT& rt, const glamr_scene_batch* b, const glamr_stage_desc* st, float* grads_out, int n_scenes, int fast = 0, int tmc = 0, bool gt = false) {
+  const int lay_len = tmc > 0 ? tmc : b->max_len;
+  const glamr_param_layout l = make_layout(b->max_persons, b->max_len);
+  std::vector<float> ws(scene_workspace_floats(b->max_persons, lay_len)), arena(fast ? scene_fast_floats(1, lay_len, 1) + (size_t)2 * 6 * lay_len : 0);
   std::vector<float> tab(2 * (size_t)(st->niters > 0 ? st->niters : 1));
-  for (int i = 0; i * 2 < (int)tab.size(); ++i) adam_coef_host(st->lr, i + 1, &tab[2 * i]);
-  sc.adam_tab = st->niters <= ADAM_TAB_MAX ? tab.data() : nullptr;
-  // the same instance the device launch would pick (single-person / camera-mode specialisations)
-  const bool single = b->n_persons[si] == 1;
-  switch (camera_mode(*st)) {
-    case 1: if (single) run_scene<0, true, 1>(rt, sc, *st, l); else run_scene<0, false, 1>(rt, sc, *st, l); break;
-    case 2: if (single) run_scene<0, true, 2>(rt, sc, *st, l); else run_scene<0, false, 2>(rt, sc, *st, l); break;
-    case 3: if (single) run_scene<0, true, 0>(rt, sc, *st, l); else run_scene<0, false, 3>(rt, sc, *st, l); break;      // (constant camera: its own instance for several persons, as on the device)
-    default: if (single) run_scene<0, true, 0>(rt, sc, *st, l); else run_scene<0, false, 0>(rt, sc, *st, l); break;
+  for (size_t i = 0; 2 * i < tab.size(); ++i) adam_coef_host(st->lr, (int)i + 1, &tab[2 * i]);
+  rt.arena_ = fast ? arena.data() : nullptr; rt.ws_ = ws.data();
+  for (int si = 0; si < n_scenes; ++si) {
+    Scene sc;
+    assemble_scene(*b, l, st, si, b->n_persons[si], b->seq_len[si], ws.data(), grads_out, sc, rt.arena_, arena.size(), 1, tmc);
+    sc.adam_tab = st->niters <= ADAM_TAB_MAX ? tab.data() : nullptr;
+    const bool single = !gt && b->n_persons[si] == 1;
+    const StageInstance inst{fast, single, gt ? 0 : instance_cam(single, camera_mode(*st)), tmc, gt};
+    const TrajGradOut go{gt ? b->g_traj_local + (size_t)si * b->max_persons * b->max_len * 11 : nullptr, b->max_persons, b->max_len};
+    bool ran = false;
+    auto run = [&](auto tag) {
+      constexpr StageInstance I = decltype(tag)::value;
+      constexpr bool have = I.fast == 0 || (I.fast == 1 && I.single && !I.gt);      // (the other arena modes are not instantiated)
+      if constexpr (have && I.gt) run_scene<I.fast, I.single, I.cam, I.tmc, true>(rt, sc, *st, l, go);
+      else if constexpr (have) run_scene<I.fast, I.single, I.cam, I.tmc>(rt, sc, *st, l);
+      ran = have;
+    };
+    if (!(with_stage_instance(inst, run) || with_instance(HostOnlyInstances{}, inst, run)) || !ran) return -3;
   }
+  return 0;
 }
 
 // scene 0 only, with the trajectory recorded
 extern "C" int hostsim_grecon_trace_stage(const glamr_scene_batch* b, const glamr_stage_desc* st, float* grads_scratch, float* params_trace, float* grads_trace) {
   if (unsupported(st)) return 2;
-  glamr_param_layout l;
-  param_layout(b->max_persons, b->max_len, l);
-  std::vector<float> ws(scene_workspace_floats(b->max_persons, b->max_len));
   TraceRT rt;
-  rt.params_out = params_trace; rt.grads_out = grads_trace; rt.stride = l.scene_stride;
-  Scene sc;
-  assemble_scene(*b, l, st, 0, b->n_persons[0], b->seq_len[0], ws.data(), grads_scratch, sc);
-  run_one(rt, b, st, l, sc, 0);
-  return 0;
+  rt.params_out = params_trace; rt.grads_out = grads_trace; rt.stride = make_layout(b->max_persons, b->max_len).scene_stride;
+  return run_scenes(rt, b, st, grads_scratch, 1);
 }
 
 extern "C" int hostsim_grecon_param_layout(int max_persons, int max_len, glamr_param_layout* out) {
@@ -77,72 +92,27 @@ extern "C" int hostsim_grecon_param_layout(int max_persons, int max_len, glamr_p
 
 extern "C" int hostsim_grecon_run_stage(const glamr_scene_batch* b, const glamr_stage_desc* st, float* grads_out) {
   if (unsupported(st)) return 2;
-  glamr_param_layout l;
-  param_layout(b->max_persons, b->max_len, l);
-  std::vector<float> ws(scene_workspace_floats(b->max_persons, b->max_len));
   HostRT rt;
-  for (int si = 0; si < b->n_scenes; ++si) {
-    Scene sc;
-    assemble_scene(*b, l, st, si, b->n_persons[si], b->seq_len[si], ws.data(), grads_out, sc);
-    run_one(rt, b, st, l, sc, si);
-  }
-  return 0;
+  return run_scenes(rt, b, st, grads_out, b->n_scenes);
 }
 
-// The full-arena single-person instances (parameters + Adam moments in the arena) with the arena in host memory; layout_len > 0 = the
-// constant-layout instance (arena / workspace laid out for GLAMR_CONST_LAYOUT_FRAMES frames, on-chip parameter blocks in that layout).
-// Must give the results of hostsim_grecon_run_stage to the bit: same arithmetic, different addresses.
+// The full-arena single-person instances (parameters + Adam moments in the arena) with the arena in host memory; const_layout = laid out for
+// GLAMR_CONST_LAYOUT_FRAMES frames.  Must give the results of hostsim_grecon_run_stage to the bit: same arithmetic, different addresses.
 extern "C" int hostsim_grecon_run_stage_arena(const glamr_scene_batch* b, const glamr_stage_desc* st, int const_layout) {
   if (unsupported(st)) return 2;
   if (b->max_persons != 1) return -1;
-  constexpr int CL = GLAMR_CONST_LAYOUT_FRAMES;
   if (const_layout && layout_frames(1, b->max_len) != CL) return -2;
-  const int lay_len = const_layout ? CL : b->max_len;
-  glamr_param_layout l;
-  param_layout(1, b->max_len, l);
-  std::vector<float> ws(scene_workspace_floats(1, lay_len));
-  const size_t fast_floats = scene_fast_floats(1, lay_len, 1) + (size_t)2 * 6 * lay_len;      // room for two keypoint rows "on chip"
-  std::vector<float> arena(fast_floats);
-  std::vector<float> tab(2 * (size_t)(st->niters > 0 ? st->niters : 1));
-  for (int i = 0; i < st->niters; ++i) adam_coef_host(st->lr, i + 1, &tab[2 * (size_t)i]);
   HostRT rt;
-  rt.arena_ = arena.data(); rt.ws_ = ws.data();
-  for (int si = 0; si < b->n_scenes; ++si) {
-    Scene sc;
-    assemble_scene(*b, l, st, si, 1, b->seq_len[si], ws.data(), nullptr, sc, arena.data(), fast_floats, 1, const_layout ? CL : 0);
-    sc.adam_tab = st->niters > 0 ? tab.data() : nullptr;
-    const int cam = camera_mode(*st);
-    if (const_layout) {
-      if (cam == 1) run_scene<1, true, 1, CL>(rt, sc, *st, l); else if (cam == 2) run_scene<1, true, 2, CL>(rt, sc, *st, l); else run_scene<1, true, 0, CL>(rt, sc, *st, l);
-    } else {
-      if (cam == 1) run_scene<1, true, 1>(rt, sc, *st, l); else if (cam == 2) run_scene<1, true, 2>(rt, sc, *st, l); else run_scene<1, true, 0>(rt, sc, *st, l);
-    }
-  }
-  return 0;
+  return run_scenes(rt, b, st, nullptr, b->n_scenes, 1, const_layout ? CL : 0);
 }
 
-// The full-arena single-person instance (parameters + Adam moments in the "on-chip" arena) WITH the gradient record: what a stage driven
-// launch by launch from outside runs on the device for one-person scenes (latent-optimisation mode, GLAMR_FLAG_KEEP_CAM_PARAMS).
+// The same instance WITH the gradient record: what a stage driven launch by launch from outside runs on the device for one-person scenes
+// (latent-optimisation mode, GLAMR_FLAG_KEEP_CAM_PARAMS).
 extern "C" int hostsim_grecon_run_stage_arena_grads(const glamr_scene_batch* b, const glamr_stage_desc* st, float* grads_out) {
   if (unsupported(st)) return 2;
   if (b->max_persons != 1) return -1;
-  glamr_param_layout l;
-  param_layout(1, b->max_len, l);
-  std::vector<float> ws(scene_workspace_floats(1, b->max_len));
-  const size_t fast_floats = scene_fast_floats(1, b->max_len, 1) + (size_t)2 * 6 * b->max_len;
-  std::vector<float> arena(fast_floats);
-  std::vector<float> tab(2 * (size_t)(st->niters > 0 ? st->niters : 1));
-  for (int i = 0; i < st->niters; ++i) adam_coef_host(st->lr, i + 1, &tab[2 * (size_t)i]);
   HostRT rt;
-  rt.arena_ = arena.data(); rt.ws_ = ws.data();
-  for (int si = 0; si < b->n_scenes; ++si) {
-    Scene sc;
-    assemble_scene(*b, l, st, si, 1, b->seq_len[si], ws.data(), grads_out, sc, arena.data(), fast_floats, 1, 0);
-    sc.adam_tab = st->niters > 0 ? tab.data() : nullptr;
-    const int cam = camera_mode(*st);
-    if (cam == 1) run_scene<1, true, 1>(rt, sc, *st, l); else if (cam == 2) run_scene<1, true, 2>(rt, sc, *st, l); else run_scene<1, true, 0>(rt, sc, *st, l);
-  }
-  return 0;
+  return run_scenes(rt, b, st, grads_out, b->n_scenes, 1);
 }
 
 // the optimiser's Adam update on a flat vector (compared bit for bit with torch.optim.Adam in tests/test_adam_exact.py)

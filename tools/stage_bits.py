@@ -14,7 +14,7 @@ from oracle.port import build
 from oracle import make_golden as mg
 from tests.grecon_common import j_local_from_oracle
 
-CASES = {   # name: (cfg, frames, persons, seeds, gap)
+CASES = {   # name: (cfg, frames, persons, seeds, gap[, options])
     'dyn300': ('glamr_dynamic', 300, 1, (0, 1, 4, 6), True),
     'dyn300_nogap': ('glamr_dynamic', 300, 1, (0, 2), False),
     'dyn120': ('glamr_dynamic', 120, 1, (0, 3), True),
@@ -22,11 +22,21 @@ CASES = {   # name: (cfg, frames, persons, seeds, gap)
     '3dpw120': ('glamr_3dpw', 120, 1, (0,), False),
     'static_multi300': ('glamr_static_multi', 300, 4, (0,), True),
     'dyn_multi90': ('glamr_dynamic_multi', 90, 2, (0,), True),
+    # small cases for the instances the seven above never reach (csrc/grecon_launch.hpp); options: iters = iterations per stage, copies = the
+    # scenes repeated that often, env = development knobs for the launches, history / traj_grad = the launch records the per-iteration loss
+    # history / writes dL/d traj_local_pred and the gradient record (both hashed)
+    'wide9': ('glamr_dynamic_multi', 48, 9, (0,), True, dict(iters=5)),                                   # 32-person build, lite arena
+    'share257': ('glamr_dynamic', 64, 1, (0,), True, dict(iters=5, copies=257)),                          # per-CU share of the LDS: arena mode 3
+    'lite2': ('glamr_dynamic_multi', 120, 2, (0,), True, dict(iters=5, env={'GLAMR_GRECON_LDS_KB_RT': '26'})),      # (26 KB: lite from 100 frames on)
+    'history': ('glamr_dynamic', 64, 1, (0, 1), True, dict(iters=5, history=True)),                       # workspace instance
+    'traj_grad': ('glamr_dynamic_multi', 64, 2, (0,), True, dict(iters=1, traj_grad=True)),               # grecon_stage_traj_grad_kernel
 }
 
 
 def run_case(L, dev, root, md, name, iters=None):
-    cfg_id, T, P, seeds, gap = CASES[name]
+    cfg_id, T, P, seeds, gap = CASES[name][:5]
+    opts = CASES[name][5] if len(CASES[name]) > 5 else {}
+    iters = opts.get('iters', iters)
     cfg = get_config(cfg_id)
     ora = build.load_optimizer(root, cfg)
     datas, jls = [], []
@@ -34,18 +44,34 @@ def run_case(L, dev, root, md, name, iters=None):
         in_dict = synth.make_in_dict(seed=s, num_frames=T, num_persons=P, smpl_model=md, gap=None if gap else (0, 0))
         d = ora.init_data(in_dict, latents=mg.latents_for(in_dict, s))
         datas.append(d); jls.append(j_local_from_oracle(ora.smpl, d))
-    packed = packing.PackedScenes(datas, jls, dev)
-    sb = packed.struct()
+    packed = packing.PackedScenes(datas * opts.get('copies', 1), jls * opts.get('copies', 1), dev)
     ws = torch.empty(L.glamr_grecon_workspace_bytes(packed.S, packed.P, packed.T), dtype=torch.uint8, device=dev)
     h = hashlib.sha1()
     seen_wd = False
-    for stage, spec in cfg['opt_stage_specs'].items():
-        sd = packing.stage_desc(spec, cfg['grecon_model_specs'], seen_wd, niters=iters)
-        seen_wd = seen_wd or ('world_dheading' in spec['opt_variables'])
-        _lib.check(L.glamr_grecon_run_stage(ctypes.byref(sb), ctypes.byref(sd), None, _lib.ptr(ws), _lib.current_stream()))
-        torch.cuda.synchronize()
-        for k, v in sorted(packed.fetch().items()):
-            h.update(np.ascontiguousarray(np.asarray(v)).tobytes())
+    saved = {k: os.environ.get(k) for k in opts.get('env', {})}
+    os.environ.update(opts.get('env', {}))
+    try:
+        for stage, spec in cfg['opt_stage_specs'].items():
+            sd = packing.stage_desc(spec, cfg['grecon_model_specs'], seen_wd, niters=iters)
+            seen_wd = seen_wd or ('world_dheading' in spec['opt_variables'])
+            extra = {}
+            if opts.get('history'):
+                extra['loss_history'] = torch.zeros((packed.S, int(sd.niters), len(packing.LOSS_IDS)), dtype=torch.float32, device=dev)
+            if opts.get('traj_grad'):
+                extra['g_traj_local'] = torch.zeros((packed.S * packed.P, packed.T, 11), dtype=torch.float32, device=dev)
+            packed.t.update(extra)
+            grads = torch.zeros_like(packed.t['params']) if opts.get('traj_grad') else None
+            sb = packed.struct()
+            _lib.check(L.glamr_grecon_run_stage(ctypes.byref(sb), ctypes.byref(sd), _lib.ptr(grads), _lib.ptr(ws), _lib.current_stream()))
+            torch.cuda.synchronize()
+            for k, v in sorted(packed.fetch().items()) + sorted((k, packed.t.pop(k).cpu().numpy()) for k in extra) + ([('grads', grads.cpu().numpy())] if grads is not None else []):
+                h.update(np.ascontiguousarray(np.asarray(v)).tobytes())
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
     return h.hexdigest()[:16]
 
 
