@@ -116,6 +116,9 @@ _SIGNATURES = {
     'glamr_grecon_cam_backward': (c_int, [POINTER(SceneBatch), POINTER(StageDesc), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'glamr_grecon_aux_terms_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'glamr_grecon_aux_terms': (c_int, [POINTER(SceneBatch), POINTER(StageDesc), POINTER(AuxDesc)] + [c_void_p] * 5 + [c_int, c_void_p, c_void_p]),
+    'glamr_grecon_aux_step_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'glamr_grecon_aux_step': (c_int, [POINTER(SceneBatch), POINTER(StageDesc), POINTER(AuxDesc), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_double, c_int, c_void_p, c_void_p]),
     'glamr_adam_step': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_int, c_void_p]),
     'glamr_adam_coef_table': (c_int, [c_double, c_int, c_void_p]),
     'glamr_adam_step_indexed': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

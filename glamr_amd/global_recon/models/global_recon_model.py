@@ -28,7 +28,7 @@ from ...lib.utils import np_transform as nt
 from ...models import latent_rng
 from ...models.prior_models import MotionTrajJointModel
 from ...models.priors import num_windows, NZ
-from .. import extra_loss_schedule, packing, stepwise
+from .. import aux_step_schedule, extra_loss_schedule, packing, stepwise
 from ..configs import get_config
 
 # (body26fk index, smpl index) pairs with identical joint names (lib/utils/joints.py:48-73,619-641 through :82-85): the 14
@@ -311,11 +311,18 @@ class GlobalReconOptimizer:
         # like the penetration term and run by the same schedule (extra_loss_schedule.AuxTerms, one launch of glamr_grecon_aux_terms per
         # iteration).  aux_loss_history[stage][name]: (scenes, iterations) UNWEIGHTED values.  Without one of the names in any stage nothing changes.
         self.aux_loss_history = {}
+        # flag_aux_on_device (NOT a reference key): a run whose only terms outside the stage kernel are those six goes through
+        # aux_step_schedule.AuxStepSchedule -- two launches per iteration, no host Python, values kept on the device until collect() -- on every
+        # entry point, optimize_resident / capture_resident / optimize_stream included.  Off (the default), or with a caller's extra_loss or
+        # the penetration term present: ExtraLossSchedule and its refusals, as before.
+        self.flag_aux_on_device = bool(g('flag_aux_on_device', False))
         packing.check_penetration(self.opt_stage_specs, self.specs)
         packing.check_aux(self.opt_stage_specs, self.specs)
         self.opt_stage_specs, self._pen_cfg, self._aux_cfg = packing.split_off_kernel(self.opt_stage_specs)
         if self._off_kernel_term() is not None:
             extra_loss_schedule.check_supported(self.specs, what=self._off_kernel_term())
+        elif self._aux_on_device():
+            extra_loss_schedule.check_supported(self.specs, what=self._aux_what())
         self.flag_filter_pose = g('flag_filter_pose', True)
         # keypoint-count filter inside filter_pose (:50-52,264-268); with HybrIK's binary scores (14 scored joints per detected frame) it is all or
         # nothing: the reference's default minimum of 15 removes every frame, 14 or less none
@@ -342,11 +349,23 @@ class GlobalReconOptimizer:
             extra_loss_schedule.check_supported(self.specs)
         self._extra_loss = fn
 
+    flag_aux_on_device = False      # (the default of grecon_model_specs.flag_aux_on_device, also for an optimiser that never ran __init__)
+
+    def _aux_what(self):
+        return extra_loss_schedule.aux_what({n for c in self._aux_cfg.values() for n in c})
+
+    def _aux_on_device(self):
+        """flag_aux_on_device takes effect: the run lists terms of packing.AUX_LOSS_IDS and neither a caller's extra_loss nor a penetration term."""
+        return self.flag_aux_on_device and bool(self._aux_cfg) and self._extra_loss is None and not self._pen_cfg
+
     def _off_kernel_term(self):
-        """None when the run has no term the stage kernel does not hold -- run_schedule serves it --, else the name a refusal gives what needs the
-        launch-by-launch schedule: the caller's term before the penetration term before the terms of packing.AUX_LOSS_IDS."""
+        """None when the run has no term the stage kernel does not hold -- run_schedule serves it -- or flag_aux_on_device takes effect --
+        AuxStepSchedule does --, else the name a refusal gives what needs the launch-by-launch schedule: the caller's term before the
+        penetration term before the terms of packing.AUX_LOSS_IDS."""
+        if self._aux_on_device():
+            return None
         return 'extra_loss' if self._extra_loss is not None else 'the penetration term (loss_cfg)' if self._pen_cfg else \
-            extra_loss_schedule.aux_what({n for c in self._aux_cfg.values() for n in c}) if self._aux_cfg else None
+            self._aux_what() if self._aux_cfg else None
 
     _WHY_OPTIMIZE_ONLY = {'extra_loss': 'while extra_loss is set: the term runs user Python in every iteration',
                           'the penetration term (loss_cfg)': 'with the penetration term in loss_cfg: the term runs launch by launch on the skinned vertices'}
@@ -358,6 +377,8 @@ class GlobalReconOptimizer:
             raise NotImplementedError('%s %s (optimize / optimize_batch only)' % (what, why))
 
     def _run_schedule_or_extra(self, packed, max_iters, has_wd=False):
+        if self._aux_on_device():
+            return aux_step_schedule.AuxStepSchedule(self, packed).run(max_iters, has_wd=has_wd)
         if self._off_kernel_term() is None:
             return self.run_schedule(packed, max_iters, has_wd=has_wd)
         return extra_loss_schedule.ExtraLossSchedule(self, packed).run(max_iters, has_wd=has_wd)
@@ -1114,6 +1135,8 @@ class GlobalReconOptimizer:
         datas, packed = self.init_resident(rin, init_forward=self.latent_mode or not self._schedule_overwrites_init())
         if self.latent_mode:
             self.run_latent_schedule(rin, packed, max_iters)
+        elif self._aux_on_device():
+            aux_step_schedule.AuxStepSchedule(self, packed).run(max_iters)
         else:
             self.run_schedule(packed, max_iters)
         return datas, packed
@@ -1236,6 +1259,8 @@ class GlobalReconOptimizer:
                     k = si * packed.P + pi
                     d['person_data'][idx]['motion_latent'] = meps[k, :num_windows(int(rin.lens[k]))].copy()
                     d['person_data'][idx]['traj_latent'] = teps[k][None].copy()
+        if packed.aux_values:      # (AuxStepSchedule's values: read back here, never inside the schedule)
+            self.aux_loss_history = aux_step_schedule.publish(self._aux_cfg, packed.aux_values)
         if self.kernel_ms is not None and packed.stage_ws:
             self.kernel_ms.extend(self.launch_ms(ws) for ws in packed.stage_ws)
         self.timings['unpack'] = time.time() - t0

@@ -283,6 +283,7 @@ class PackedScenes:
         self.person_arrays = self.exists = self.keepalive = self.latents = self.last_ws = None
         self.root_trans_cam = None      # (S * P, T, 3) the persons' pd['root_trans_cam'] of a batch packed from host dictionaries (cam_traj_trans reads it)
         self.stage_ws = []
+        self.aux_values = None          # {stage: (S, iterations, 6)} on the device: aux_step_schedule.AuxStepSchedule's values of the last schedule (collect() publishes them)
 
     @classmethod
     def empty(cls, n_scenes, max_persons, max_len, device, with_rel=None, seq_names=None):

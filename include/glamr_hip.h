@@ -510,6 +510,30 @@ int glamr_grecon_aux_terms(const glamr_scene_batch* batch, const glamr_stage_des
                            float* grads /* (n_scenes, scene_stride), the layout of grads_out */,
                            int accumulate /* 1: add, 0: zero-fill the given outputs first */, void* workspace, void* stream);
 
+/* Everything that follows the gradient launch in an Adam iteration of a stage whose loss_cfg lists terms of glamr_grecon_aux_terms, in ONE
+ * launch (csrc/grecon_aux_step.hpp): per scene, glamr_grecon_aux_terms in add mode on zeroed scratch adjoints (loss_func.py:60-73,
+ * 94-103, 135-144, 175-186, 216-217), glamr_grecon_cam_backward on the scratch g_cam_pose (global_recon_model.py:473-508) when a term outside
+ * the monitor mask writes to it, glamr_grecon_pose_backward on every present slot (:394-426, 459-465) when a pose adjoint is live, both
+ * accumulating into `grads`, and one torch.optim.Adam step (torch/optim/adam.py _single_tensor_adam, :642) on the scene's row of
+ * batch->params / exp_avg / exp_avg_sq with `lr` and the 1-based `step` as glamr_adam_step takes them -- the `loss.backward()` and
+ * `optimizer.step()` of :556-557 for these terms.  The same code as the three entry points, a workgroup barrier where they have a launch
+ * boundary.  grads: dev (n_scenes, scene_stride), in: the stage kernel's gradient (grads_out of a launch with niters 1 and lr 0), out: the
+ * iteration's complete gradient; never cleared.  values: dev (n_scenes, values_stride) floats, the six UNWEIGHTED values of this call are
+ * written at [scene][6 iteration ... 6 iteration + 5] (values_stride >= 6 (iteration + 1): a stage's (n_scenes, n_iterations, 6) history).
+ * `iteration` and `step` are plain arguments: every iteration is a launch, and a graph node, of its own.  stage: var_mask and flags are read
+ * (GLAMR_FLAG_HAS_WORLD_DHEADING as glamr_grecon_pose_backward reads it).  Refused with the codes of the composed calls: max_len < 2 and the
+ * other geometry limits (GLAMR_E_INVALID), batch->frozen != NULL and GLAMR_FLAG_ABSOLUTE_HEADING (GLAMR_E_UNSUPPORTED), the camera-variable
+ * terms without GLAMR_VAR_CAM (GLAMR_E_UNSUPPORTED).  Never read: what the three calls document as never read.  One workgroup of 256 threads
+ * per scene, one instance per camera mode; no atomics, fixed summation order: two calls give the same bits.  After its argument checks the
+ * call reads no host memory and does not synchronise: it can be recorded into a stream capture.  workspace:
+ * glamr_grecon_aux_step_workspace_bytes, device memory, contents irrelevant before and after. */
+size_t glamr_grecon_aux_step_workspace_bytes(int n_scenes, int max_persons, int max_len);
+int glamr_grecon_aux_step(const glamr_scene_batch* batch, const glamr_stage_desc* stage, const glamr_aux_desc* aux,
+                          const float* root_trans_cam /* (slots, max_len, 3), or NULL without cam_traj_trans */,
+                          float* values /* (n_scenes, values_stride) */, int values_stride, int iteration /* 0-based */,
+                          float* grads /* (n_scenes, scene_stride) in / out */, float* exp_avg, float* exp_avg_sq /* (n_scenes, scene_stride) */,
+                          double lr, int step /* 1-based */, void* workspace, void* stream);
+
 /* One torch.optim.Adam step (betas 0.9 / 0.999, eps 1e-8, no weight decay; torch/optim/adam.py _single_tensor_adam, the path
  * GlobalReconOptimizer.init_opt selects, global_recon_model.py:642) on a flat fp32 vector, with the update function the fused
  * optimiser uses: operation order of torch's CPU kernels, IEEE quotient / square root, `lr` and the bias corrections formed in double
