@@ -1,12 +1,17 @@
 """Headline benchmark: sequences/sec of end-to-end global reconstruction (GlobalReconOptimizer.optimize_resident) on 300-frame,
 1-person, dynamic-camera synthetic sequences (BASELINE.json configs[1], cfg `glamr_dynamic`, 500 Adam iterations).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--mode weak|strong --total 64] [--seed S] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--mode weak|strong --total 64] [--seed S] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: set-up, warm-up, capture and check of the step graphs, the timed steps, --dump-outputs,
+the check of the replays, and the result line (metric, value, ms_per_step, config, replay_check).  `--full` adds, after the timed steps, every
+other measurement described below -- the roofline block, `pipeline`, the host-inclusive rates, the strong line, one sequence's latency, the
+person-sharded line, `kernels`, `cpu_baseline` -- each still behind its own --no-... switch; the timed steps are the same either way.
 
 A "step" = one pass of the hot path over one batch of B independent synthetic sequences per GPU: per-person preparation of the
 HybrIK arrays, motion infilling + trajectory prediction, SMPL skinning, scene initialisation and the full optimisation schedule.
 The HybrIK arrays are uploaded once before the timed region (stage_inputs), so `value` is the HBM-in / HBM-out rate the contract asks
-for; the rate from HOST dictionaries to HOST dictionaries (optimize_batch / the pipelined optimize_stream) is measured after it and
+for; the rate from HOST dictionaries to HOST dictionaries (optimize_batch / the pipelined optimize_stream) is measured after it with --full and
 reported as `host_inclusive_sequences_per_sec`.  Multi-GPU: one process per GPU (torch.distributed over RCCL), sequences are
 independent, so ranks share nothing on the data path; the only collectives are the barrier and the max-reduction of the elapsed
 time.  `--mode weak` (default): every rank works on its own B sequences; `--mode strong --total 64`: BASELINE configs[2], a fixed set
@@ -26,7 +31,7 @@ themselves on the LDS kernels.
 Kernel durations come from the kernel's own clock (stamps in the workspace header = what rocprofv3 reports for the dispatch), and the
 roofline launch is measured with the GPU to itself (see run()).
 
-Prints ONE JSON line on rank 0:
+Prints ONE JSON line on rank 0; with --full it also holds:
   roofline      the dominant kernel (the fused optimiser stage).  It is LATENCY / ISSUE bound: `us_per_scene_iteration` against the
                 1.45 us dependent-boundary floor is the figure that describes it; `achieved` / `frac` are the contract's NOTIONAL HBM line
                 (SURVEY 8d's live-state bytes over the launch time -- bytes the kernel keeps on chip and does not move); `traffic` are the
@@ -520,6 +525,9 @@ def run(argv=None):
     ap.add_argument('--seed', type=int, default=0, help='seed of the generators the latent draws of the priors come from (rank r: seed + r); the same arguments, the same inputs')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write what the LAST timed step computed (rank 0: the arrays a caller of '
                     'optimize_resident receives, for a fixed, seeded sample of %d scenes of the batch) as DIR/<name>.npy, float32 / float64' % DUMP_SCENES)
+    ap.add_argument('--full', action='store_true', help='after the timed steps, also measure everything beside the headline: the stage kernel\'s roofline block and its launches '
+                    'beside the priors, the BASELINE configs[2] strong line, the host-inclusive rates, one sequence\'s latency, the person-sharded configs[3] and its '
+                    'collectives, the stand-alone kernel lines and the CPU baseline (each still subject to its --no-... switch).  Default: the headline alone')
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error('--steps must be at least 1')
@@ -704,7 +712,7 @@ def run(argv=None):
             raise SystemExit('bench: the pipelined replays do NOT reproduce plain steps (max %.3g px): no number is reported for a timing of wrong results'
                              % replay_check['max_projection_difference_px'])
     beside = None
-    if coschedule:
+    if coschedule and args.full:
         # what a stage launch takes in THIS pipeline (beside the other stream's priors): four more gated steps as plain launches, whose
         # workspaces carry the kernel's own clock stamps (graph replays share one workspace per graph) -- after the clock has stopped
         try:
@@ -715,6 +723,7 @@ def run(argv=None):
             beside = [round(model.launch_ms(ws), 2) for wss in stage_events[2:5] for ws in wss]      # (the last one has no neighbour)
         except Exception as e:      # noqa: BLE001
             sys.stderr.write('bench: co-scheduled stage launches not measured (%s)\n' % e)
+    if coschedule:
         del stage_events[:]
         model.pipeline_gate = None                                   # the single-stream measurements below run the plain step
     if coschedule and args.no_early_prep:
@@ -723,7 +732,7 @@ def run(argv=None):
     n_total = parallel.sum_over_ranks(B, dev)                      # units all ranks processed per step
     rccl_ranks = dist.get_world_size() if (use_dist and dist.get_backend() == 'nccl') else None
     strong = None
-    if args.mode == 'weak' and not args.no_strong_line:
+    if args.full and args.mode == 'weak' and not args.no_strong_line:
         gate_keep, model.pipeline_gate = getattr(model, 'pipeline_gate', None), None
         strong = strong_line(model, md, rank, world, dev, args.total, max(2, min(5, args.steps)), sync, use_dist)
         model.pipeline_gate = gate_keep
@@ -732,12 +741,36 @@ def run(argv=None):
                'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True,
                'scaling': args.mode, 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic', 'config': {'workload': 'STUB (CPU test of the skeleton)', 'sequences_total': n_total,
                                                                                                           'seeds_first_last': [int(seeds[0]), int(seeds[-1])]},
-               'rccl_ranks': rccl_ranks, 'process_group_ranks': dist.get_world_size() if use_dist else None, 'configs2_strong_64': strong}
+               'rccl_ranks': rccl_ranks, 'process_group_ranks': dist.get_world_size() if use_dist else None, 'configs2_strong_64': strong, 'full': args.full}
         if rank == 0:
             print(json.dumps(out))
         if use_dist:
             dist.destroy_process_group()
         return out if rank == 0 else None
+
+    iters = sum(s['opt_niters'] for s in model.opt_stage_specs.values())
+    n_cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    # the headline: what every run reports, a plain one nothing else
+    head = {
+        'metric': 'sequences/sec (300-frame, 1-person) end-to-end global_recon', 'value': n_total * args.steps / elapsed,
+        'unit': 'sequences/sec', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True, 'scaling': args.mode, 'vs_baseline': None,
+        'dtype': 'f32 (optimiser, init_data) / fp16x2-split MFMA with f32 accumulation (priors, LBS: every f32 operand as hi + lo fp16 planes, hi*hi + hi*lo + lo*hi)',
+        'data': 'synthetic', 'host_enqueue_ms_per_step': enqueue / args.steps * 1e3,
+        'rccl_ranks': rccl_ranks, 'process_group_ranks': dist.get_world_size() if use_dist else None,
+        'config': {'workload': ('BASELINE configs[1]: %d-frame 1-person dynamic-camera sequences, cfg %s (%d Adam iterations), batch of %d independent '
+                                'sequences per GPU, HybrIK arrays resident in HBM%s' % (NUM_FRAMES, CFG_ID, iters, B, '; the step is replayed as one captured HIP graph per stream (bit-checked against plain launches)' if step_graphs else '')) if args.mode == 'weak' else
+                               ('BASELINE configs[2]: %d independent %d-frame 1-person sequences (cfg %s, %d iterations) split over %d GPU(s): %d per GPU '
+                                '= %d of %d CUs busy in the optimiser stage' % (args.total, NUM_FRAMES, CFG_ID, iters, world, B, min(B, n_cus), n_cus)),
+                   'sequences_per_gpu': B, 'frames': NUM_FRAMES, 'persons': 1, 'parallelism': 'sequence-sharded x%d' % world,
+                   'streams_per_gpu': len(streams), 'step_graph': bool(step_graphs), 'coscheduled_streams': bool(coschedule)},
+        'full': args.full, 'replay_check': replay_check, 'dump_outputs': dumped}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head))
+        if use_dist:
+            dist.destroy_process_group()
+        return head if rank == 0 else None
 
     # one entry per optimiser-stage launch in the timed region: the kernel's own clock (earliest workgroup start to latest workgroup
     # end, what rocprofv3 reports for the dispatch) -- HIP events around the launch would also count the time it waits behind the
@@ -819,9 +852,7 @@ def run(argv=None):
 
     out = None
     if rank == 0:
-        iters = sum(s['opt_niters'] for s in model.opt_stage_specs.values())
         k_avg = sum(kms) / max(1, len(kms))
-        n_cus = torch.cuda.get_device_properties(dev).multi_processor_count
         rounds = -(-B // n_cus)                                      # one 300-frame scene per CU at a time
         us_scene_iter = k_avg * 1e3 / iters / rounds
         algo_bytes = B * iters * ALGO_BYTES_PER_PERSON_ITER
@@ -850,19 +881,8 @@ def run(argv=None):
                               'one_wave_us': valu_wave_iter * 2 / clock_hz * 1e6, 'busiest_simd_us': 2 * valu_wave_iter * 2 / clock_hz * 1e6}
                 valu_issue['frac_of_one_wave'] = valu_issue['one_wave_us'] / us_scene_iter if us_scene_iter > 0 else None
                 valu_issue['frac_of_busiest_simd'] = valu_issue['busiest_simd_us'] / us_scene_iter if us_scene_iter > 0 else None
-        out = {
-            'metric': 'sequences/sec (300-frame, 1-person) end-to-end global_recon', 'value': n_total * args.steps / elapsed,
-            'unit': 'sequences/sec', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True, 'scaling': args.mode, 'vs_baseline': None,
-            'dtype': 'f32 (optimiser, init_data) / fp16x2-split MFMA with f32 accumulation (priors, LBS: every f32 operand as hi + lo fp16 planes, hi*hi + hi*lo + lo*hi)',
-            'data': 'synthetic', 'host_enqueue_ms_per_step': enqueue / args.steps * 1e3,
-            'rccl_ranks': rccl_ranks, 'process_group_ranks': dist.get_world_size() if use_dist else None,
-            'config': {'workload': ('BASELINE configs[1]: %d-frame 1-person dynamic-camera sequences, cfg %s (%d Adam iterations), batch of %d independent '
-                                    'sequences per GPU, HybrIK arrays resident in HBM%s' % (NUM_FRAMES, CFG_ID, iters, B, '; the step is replayed as one captured HIP graph per stream (bit-checked against plain launches)' if step_graphs else '')) if args.mode == 'weak' else
-                                   ('BASELINE configs[2]: %d independent %d-frame 1-person sequences (cfg %s, %d iterations) split over %d GPU(s): %d per GPU '
-                                    '= %d of %d CUs busy in the optimiser stage' % (args.total, NUM_FRAMES, CFG_ID, iters, world, B, min(B, n_cus), n_cus)),
-                       'sequences_per_gpu': B, 'frames': NUM_FRAMES, 'persons': 1, 'parallelism': 'sequence-sharded x%d' % world,
-                       'streams_per_gpu': len(streams), 'step_graph': bool(step_graphs), 'coscheduled_streams': bool(coschedule)},
+        out = dict(head)
+        out.update({
             'roofline': {'kernel': 'grecon_stage_kernel<1,true,1,304>', 'bound': 'latency/issue',
                          'bound_note': 'one workgroup per scene, state on chip, 7 workgroup barriers per iteration; neither HBM nor the matrix pipes limit it.  Round 5 removed the exposed '
                                        'memory waits of the dependent chain (13.3 -> 10.6 us per scene-iteration, profiles/r05_stage_ab.log); what bounds it now is ISSUE on the SIMD that '
@@ -890,7 +910,6 @@ def run(argv=None):
                                       '2 single-stream plain steps right after the timed region: in the timed region the launches of the %d stream(s) '
                                       'share the CUs%s' % (len(streams), ' and are graph replays (one workspace per graph: no per-replay stamps)' if step_graphs else '')),
                          'note': 'traffic = memory-side bytes of one launch (rocprofv3 PMC passes on the shipped instance)'},
-            'replay_check': replay_check, 'dump_outputs': dumped,
             'pipeline': None if not coschedule else {
                 'coscheduled_streams': True, 'stage_launch_ms_alone': k_avg, 'stage_launch_ms_beside_the_priors': beside,
                 'critical_cycle': 'per batch and stream -- preparation (ahead of the gate: three-graph cut), infiller I beside the other batch\'s stage (~27 ms), then, when '
@@ -908,7 +927,7 @@ def run(argv=None):
             'host_inclusive_single_call_sequences_per_sec': B / host_single,
             'host_inclusive_first_call_on_a_new_stream_sequences_per_sec': B / host_first,
             'host_inclusive_stage_seconds': {k: round(v, 4) for k, v in tm.items()},
-        }
+        })
         if strong is not None:
             out['configs2_strong_64'] = strong
         if sharded4 is not None:

@@ -765,8 +765,9 @@ def test_bench_runs_under_an_rccl_process_group_of_one_rank(monkeypatch):
     s.close()
     for k, v in (('MASTER_ADDR', '127.0.0.1'), ('MASTER_PORT', str(port)), ('RANK', '0'), ('LOCAL_RANK', '0'), ('WORLD_SIZE', '1')):
         monkeypatch.setenv(k, v)
-    out = bench.run(['--gpus', '1', '--steps', '2', '--warmup', '1', '--batch', '64', '--no-cpu-baseline', '--no-kernel-lines', '--force-dist'])
+    out = bench.run(['--gpus', '1', '--steps', '2', '--warmup', '1', '--batch', '64', '--full', '--no-cpu-baseline', '--no-kernel-lines', '--force-dist'])
     assert out['n_gpus'] == 1 and out['value'] > 0 and out['config']['step_graph'] is True
+    assert out['full'] is True and out['roofline']['avg_launch_ms'] > 0 and out['host_inclusive_sequences_per_sec'] > 0
     coll = out['collective_alternative']
     assert coll['ranks'] == 1 and 0 < coll['us_per_iteration_allreduce9_plus_allgather_4x300x12'] < 5e3
     import torch.distributed as dist

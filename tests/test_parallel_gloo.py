@@ -123,7 +123,7 @@ def test_bench_launched_plainly_spawns_its_own_ranks():
     import subprocess
     import sys
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--stub-model', '--backend', 'gloo', '--steps', '3', '--warmup', '1',
-                        '--batch', '6'], env=_plain_env(), capture_output=True, text=True, timeout=300, cwd=ROOT)
+                        '--batch', '6', '--full'], env=_plain_env(), capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout
