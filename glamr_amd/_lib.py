@@ -30,6 +30,11 @@ class SceneBatch(Structure):
                                         'kp_2d_pred', 'orient_cam_in_world', 'frozen', 'g_j_local', 'g_traj_local', 'loss_history')]
 
 
+class StageExt(Structure):      # glamr_stage_ext (glamr_grecon_run_stage_ext: world_dxy / world_res and their regularisers)
+    _fields_ = [('var_mask', c_uint32), ('flags', c_uint32), ('loss_mask', c_uint32), ('monitor_mask', c_uint32), ('loss_weight', c_float * 2)] + \
+               [(n, c_void_p) for n in ('residuals', 'grads', 'losses', 'loss_history', 'workspace')]
+
+
 AUX_NUM_TERMS = 6           # GLAMR_AUX_NUM_TERMS: the terms of glamr_grecon_aux_terms (packing.AUX_LOSS_IDS names them)
 
 
@@ -109,6 +114,8 @@ _SIGNATURES = {
     'glamr_grecon_param_layout': (c_int, [c_int, c_int, POINTER(ParamLayout)]),
     'glamr_grecon_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'glamr_grecon_run_stage': (c_int, [POINTER(SceneBatch), POINTER(StageDesc), c_void_p, c_void_p, c_void_p]),
+    'glamr_grecon_ext_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'glamr_grecon_run_stage_ext': (c_int, [POINTER(SceneBatch), POINTER(StageDesc), POINTER(StageExt), c_void_p, c_void_p, c_void_p]),
     'glamr_grecon_last_launch_ns': (c_int, [c_void_p, POINTER(ctypes.c_double)]),
     'glamr_grecon_pose_backward_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'glamr_grecon_pose_backward': (c_int, [POINTER(SceneBatch), POINTER(StageDesc), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),

@@ -87,6 +87,37 @@ __global__ __launch_bounds__(MAX_THREADS, WAVES_PER_EU) void grecon_stage_traj_g
   if (threadIdx.x == 0) atomicMax(a.stamps + 1, (unsigned long long)wall_clock64());
 }
 
+#ifdef GLAMR_GRECON_WIDE
+// The instances of a launch with the world-frame residuals (glamr_grecon_run_stage_ext: world_dxy, world_res and their regularisers).  Kernels of
+// their own, in this compile only: every other instance, its argument block included, is what it was.
+struct KernelArgsExt { KernelArgs a; glamr_stage_ext ext; };
+template <int FAST>
+__global__ __launch_bounds__(MAX_THREADS, WAVES_PER_EU) void grecon_stage_ext_kernel(KernelArgsExt ax) {
+  __shared__ __attribute__((aligned(16))) float red[RT_RED_FLOATS];
+  __shared__ Scene sc;
+  __shared__ glamr_stage_desc s_st;
+  __shared__ glamr_param_layout s_lay;
+  __shared__ SceneExt s_x;
+  extern __shared__ __attribute__((aligned(16))) float arena[];
+  const KernelArgs& a = ax.a;
+  const int si = blockIdx.x;
+  __builtin_amdgcn_s_setprio(3);
+  if (threadIdx.x == 0) {
+    atomicMin(a.stamps, (unsigned long long)wall_clock64());
+    s_st = a.st;
+    s_lay = a.lay;
+    assemble_scene(a.b, s_lay, &s_st, si, a.b.n_persons[si], a.b.seq_len[si], a.workspace + (size_t)si * a.ws_floats_per_scene, a.grads_out, sc,
+                   a.use_lds ? arena : nullptr, a.fast_floats, a.use_lds, a.layout_len);
+    sc.adam_tab = a.adam_tab;
+    bind_ext(s_x, a.b, ax.ext, si, a.st.niters);
+  }
+  __syncthreads();
+  glamr::DeviceRT rt{red, a.workspace + (size_t)si * a.ws_floats_per_scene};
+  run_scene<FAST, false, 0, 0, false, true>(rt, sc, a.st, a.lay, TrajGradOut{nullptr, 0, 0}, &s_x);
+  if (threadIdx.x == 0) atomicMax(a.stamps + 1, (unsigned long long)wall_clock64());
+}
+#endif
+
 }  // namespace GLAMR_GRECON_NS
 }  // namespace glamr
 
@@ -100,10 +131,13 @@ constexpr int WIDE_MAX_PERSONS = 32;
 #ifdef GLAMR_GRECON_WIDE
 #define glamr_grecon_workspace_bytes glamr_grecon_workspace_bytes_wide_
 #define glamr_grecon_run_stage glamr_grecon_run_stage_wide_
+#define GLAMR_STAGE_EXT_PARAM , const glamr_stage_ext* ext
 static_assert(MAXP == WIDE_MAX_PERSONS, "grecon_wide.hip sets GLAMR_MAX_PERSONS");
 #else
 extern "C" size_t glamr_grecon_workspace_bytes_wide_(int n_scenes, int max_persons, int max_len);
-extern "C" int glamr_grecon_run_stage_wide_(const glamr_scene_batch* batch, const glamr_stage_desc* stage, float* grads_out, void* workspace, void* stream_);
+extern "C" int glamr_grecon_run_stage_wide_(const glamr_scene_batch* batch, const glamr_stage_desc* stage, float* grads_out, void* workspace, void* stream_,
+                                            const glamr_stage_ext* ext);
+#define GLAMR_STAGE_EXT_PARAM
 
 extern "C" int glamr_grecon_param_layout(int max_persons, int max_len, glamr_param_layout* out) {
   GLAMR_REQUIRE(out && max_persons >= 1 && max_persons <= WIDE_MAX_PERSONS && max_len >= 2, "bad arguments (1 <= max_persons <= %d, max_len >= 2)", WIDE_MAX_PERSONS);
@@ -161,14 +195,15 @@ int adam_table(double lr, int niters, const float** out) {
   return GLAMR_OK;
 }
 // launches the plan's instance; its dynamic-LDS limit is raised once per (device, instance) and process (a driver call per launch is host time on every step)
-int launch_stage(void (*kern)(KernelArgs), const StagePlan& plan, int dev, hipStream_t stream, const KernelArgs& ka) {
+template <class Args>
+int launch_stage(void (*kern)(Args), const StagePlan& plan, int dev, hipStream_t stream, const Args& ka, int n_scenes) {
   if (plan.lds_bytes) {
     static std::mutex mu; static std::set<std::pair<int, const void*>> raised;
     std::lock_guard<std::mutex> lock(mu);
     if (raised.insert(std::make_pair(dev, reinterpret_cast<const void*>(kern))).second)
       GLAMR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX));
   }
-  hipLaunchKernelGGL(kern, dim3(ka.b.n_scenes), dim3(plan.threads), plan.lds_bytes, stream, ka);
+  hipLaunchKernelGGL(kern, dim3(n_scenes), dim3(plan.threads), plan.lds_bytes, stream, ka);
   return GLAMR_OK;
 }
 int current_device() {
@@ -190,14 +225,43 @@ extern "C" size_t glamr_grecon_workspace_bytes(int n_scenes, int max_persons, in
   return GLAMR_GRECON_WS_HEADER + (size_t)n_scenes * align_up(scene_workspace_floats(max_persons, layout_frames(max_persons, max_len)), 64) * sizeof(float);
 }
 
+#ifndef GLAMR_GRECON_WIDE
+namespace { int run_stage_any(const glamr_scene_batch* batch, const glamr_stage_desc* stage, const glamr_stage_ext* ext, float* grads_out, void* workspace, void* stream_); }
+extern "C" int glamr_grecon_run_stage(const glamr_scene_batch* batch, const glamr_stage_desc* stage, float* grads_out, void* workspace, void* stream_) {
+  return run_stage_any(batch, stage, nullptr, grads_out, workspace, stream_);
+}
+// per slot and frame: Adam's two moments of the 8 residual numbers and the rotation columns before the orientation residual (grecon_algo.hpp EXT_WS)
+extern "C" size_t glamr_grecon_ext_workspace_bytes(int n_scenes, int max_persons, int max_len) {
+  if (n_scenes <= 0 || max_persons < 1 || max_persons > WIDE_MAX_PERSONS || max_len < 2) return 0;
+  return (size_t)n_scenes * max_persons * max_len * EXT_WS * sizeof(float);
+}
+extern "C" int glamr_grecon_run_stage_ext(const glamr_scene_batch* batch, const glamr_stage_desc* stage, const glamr_stage_ext* ext, float* grads_out,
+                                          void* workspace, void* stream_) {
+  if (ext) {
+    GLAMR_REQUIRE(batch && stage && workspace, "null argument");
+    GLAMR_REQUIRE(ext->residuals && ext->losses && ext->workspace, "a required array of glamr_stage_ext is NULL");
+    GLAMR_REQUIRE(!(ext->var_mask & ~(GLAMR_EXT_VAR_WORLD_DXY | GLAMR_EXT_VAR_WORLD_RES)) && !(ext->flags & ~(GLAMR_EXT_HAS_WORLD_DXY | GLAMR_EXT_APPLY_WORLD_RES)) &&
+                      !(ext->loss_mask >> GLAMR_EXT_NUM_LOSSES) && !(ext->monitor_mask >> GLAMR_EXT_NUM_LOSSES), "unknown bits in glamr_stage_ext");
+    if (batch->frozen) return fail(GLAMR_E_UNSUPPORTED, "glamr_grecon_run_stage_ext: person-sharded batches (glamr_scene_batch.frozen) are not supported with the world-frame residuals");
+    if (batch->g_traj_local) return fail(GLAMR_E_UNSUPPORTED, "glamr_grecon_run_stage_ext: g_traj_local is not supported with the world-frame residuals");
+  }
+  return run_stage_any(batch, stage, ext, grads_out, workspace, stream_);
+}
+#endif
+
+#ifdef GLAMR_GRECON_WIDE
 extern "C" int glamr_grecon_run_stage(const glamr_scene_batch* batch, const glamr_stage_desc* stage, float* grads_out,
-                                      void* workspace, void* stream_) {
+                                      void* workspace, void* stream_ GLAMR_STAGE_EXT_PARAM) {
+#else
+namespace {
+int run_stage_any(const glamr_scene_batch* batch, const glamr_stage_desc* stage, const glamr_stage_ext* ext, float* grads_out, void* workspace, void* stream_) {
+#endif
   GLAMR_REQUIRE(batch && stage && workspace, "null argument");
   GLAMR_REQUIRE(batch->n_scenes > 0 && batch->max_persons >= 1 && batch->max_persons <= WIDE_MAX_PERSONS && batch->max_len >= 2,
                 "bad batch geometry: n_scenes=%d max_persons=%d (at most %d) max_len=%d", batch->n_scenes, batch->max_persons, WIDE_MAX_PERSONS, batch->max_len);
 #ifndef GLAMR_GRECON_WIDE
-  if (batch->max_persons > MAXP || (stage && (stage->flags & GLAMR_FLAG_ABSOLUTE_HEADING))) {
-    const int rc = glamr_grecon_run_stage_wide_(batch, stage, grads_out, workspace, stream_);
+  if (batch->max_persons > MAXP || (stage && (stage->flags & GLAMR_FLAG_ABSOLUTE_HEADING)) || ext) {
+    const int rc = glamr_grecon_run_stage_wide_(batch, stage, grads_out, workspace, stream_, ext);
     if (rc == GLAMR_OK) record_launch(workspace, static_cast<hipStream_t>(stream_));
     return rc;
   }
@@ -236,8 +300,13 @@ extern "C" int glamr_grecon_run_stage(const glamr_scene_batch* batch, const glam
   int rc = GLAMR_OK;
   const bool known = with_stage_instance(plan.inst, [&](auto tag) {
     constexpr StageInstance I = decltype(tag)::value;
-    if constexpr (I.gt) rc = launch_stage(grecon_stage_traj_grad_kernel<I.fast>, plan, dev, stream, ka);
-    else rc = launch_stage(grecon_stage_kernel<I.fast, I.single, I.cam, I.tmc>, plan, dev, stream, ka);
+#ifdef GLAMR_GRECON_WIDE
+    if constexpr (!I.gt) {
+      if (ext) { rc = launch_stage(grecon_stage_ext_kernel<I.fast>, plan, dev, stream, KernelArgsExt{ka, *ext}, ka.b.n_scenes); return; }
+    }
+#endif
+    if constexpr (I.gt) rc = launch_stage(grecon_stage_traj_grad_kernel<I.fast>, plan, dev, stream, ka, ka.b.n_scenes);
+    else rc = launch_stage(grecon_stage_kernel<I.fast, I.single, I.cam, I.tmc>, plan, dev, stream, ka, ka.b.n_scenes);
   });
   GLAMR_REQUIRE(known, "no stage kernel instance FAST=%d SINGLE=%d CAM=%d TMC=%d GT=%d", plan.inst.fast, plan.inst.single, plan.inst.cam, plan.inst.tmc, plan.inst.gt);
   if (rc) return rc;
@@ -247,6 +316,9 @@ extern "C" int glamr_grecon_run_stage(const glamr_scene_batch* batch, const glam
 #endif
   return GLAMR_OK;
 }
+#ifndef GLAMR_GRECON_WIDE
+}  // namespace
+#endif
 
 #ifndef GLAMR_GRECON_WIDE
 namespace {

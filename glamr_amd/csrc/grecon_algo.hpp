@@ -788,8 +788,38 @@ template <int TMC> struct OnChipLayout { static constexpr glamr_param_layout val
 // person slot, [max_persons][max_len][11].  Only the launches that ask for it run GT instances; every other instance is compiled without a
 // trace of it (the stores, their address arithmetic and the pointer are template-dependent, and the scene description is not touched).
 struct TrajGradOut { float* base; int max_persons, max_len; };      // (the two in glamr_scene_batch's order: copied as a pair)
-template <int FAST, bool SINGLE, int CAM, int TMC = 0, bool GT = false, class RT>
-GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const glamr_param_layout& l, TrajGradOut gt = TrajGradOut{nullptr, 0, 0}) {
+constexpr int EXT_WS = 24;      // floats per slot and frame of glamr_stage_ext.workspace (below; glamr_grecon_ext_workspace_bytes sizes it in either compile)
+#ifdef GLAMR_GRECON_WIDE
+// World-frame residuals (glamr_stage_ext: world_dxy, world_res, traj_rot_res / traj_trans_res; global_recon_model.py:452-468, loss_func.py:189-209),
+// bound to one scene.  Only this compile knows them: the reference adds them to a frame's world pose from that frame's own elements, so phases C and
+// H take them without a scan, a barrier or an exchange array.  `ws`: per slot and frame EXT_WS floats -- Adam's m (8), v (8), and the two stored
+// columns of R_w BEFORE the orientation residual (6), which phase H needs to carry the adjoint on into the trajectory chain.
+static_assert(EXT_WS >= 8 + 8 + 6, "m at 0, v at 8, the two columns at 16");
+struct SceneExt {
+  unsigned var_mask, flags, loss_mask, monitor_mask;
+  float weight[GLAMR_EXT_NUM_LOSSES];
+  float *res, *g, *ws, *losses, *hist;      // this scene's first slot / row; g, hist or null
+  int TB;                                   // frames per slot of those arrays (the batch's max_len)
+};
+GLAMR_HD void bind_ext(SceneExt& x, const glamr_scene_batch& b, const glamr_stage_ext& e, int si, int niters) {
+  const size_t row0 = (size_t)si * b.max_persons * b.max_len;
+  x.var_mask = e.var_mask; x.flags = e.flags; x.loss_mask = e.loss_mask; x.monitor_mask = e.monitor_mask;
+  for (int k = 0; k < GLAMR_EXT_NUM_LOSSES; ++k) x.weight[k] = e.loss_weight[k];
+  x.res = e.residuals + row0 * GLAMR_EXT_FLOATS;
+  x.g = e.grads ? e.grads + row0 * GLAMR_EXT_FLOATS : nullptr;
+  x.ws = static_cast<float*>(e.workspace) + row0 * EXT_WS;
+  x.losses = e.losses + (size_t)si * GLAMR_EXT_NUM_LOSSES;
+  x.hist = (e.loss_history && b.loss_history && niters > 0) ? e.loss_history + (size_t)si * niters * GLAMR_EXT_NUM_LOSSES : nullptr;
+  x.TB = b.max_len;
+}
+#endif
+// EXT: the instance also carries the world-frame residuals (`sx`; csrc/grecon_wide.hip's compile only, kernels of their own).
+template <int FAST, bool SINGLE, int CAM, int TMC = 0, bool GT = false, bool EXT = false, class RT>
+GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const glamr_param_layout& l, TrajGradOut gt = TrajGradOut{nullptr, 0, 0}
+#ifdef GLAMR_GRECON_WIDE
+                        , const SceneExt* sx = nullptr
+#endif
+) {
   static_assert(!GT || TMC == 0, "the trajectory-row gradient is not written by the constant-layout instances");
   [[maybe_unused]] auto gt_row = [&](int p, int e) { return glob(gt.base) + ((size_t)p * gt.max_len + e) * 11; };
   constexpr bool AF = FAST == 1 && SINGLE;          // parameters + Adam moments on chip (assemble_scene: adam_fast)
@@ -827,6 +857,19 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
   auto on = [&](int id) { return (st.loss_mask >> id) & 1u; };
   auto active = [&](int id) { return ((st.loss_mask >> id) & 1u) && !((st.monitor_mask >> id) & 1u); };
   auto ffo = [&](int id) { return (st.first_frame_only_mask >> id) & 1u; };
+#ifdef GLAMR_GRECON_WIDE
+  // the extension's uniform scalars, copied out of the (LDS) description once; its arrays are all global
+  static_assert(!EXT || (!GT && !SINGLE && TMC == 0), "the world-frame residuals run on the general instances");
+  constexpr bool x_on = EXT;
+  const unsigned x_flags = x_on ? (unsigned)uni((int)sx->flags) : 0u, x_var = x_on ? (unsigned)uni((int)sx->var_mask) : 0u;
+  const unsigned x_lmask = x_on ? (unsigned)uni((int)sx->loss_mask) : 0u, x_mon = x_on ? (unsigned)uni((int)sx->monitor_mask) : 0u;
+  const bool x_has_dxy = (x_flags & GLAMR_EXT_HAS_WORLD_DXY) || (x_var & GLAMR_EXT_VAR_WORLD_DXY);
+  const bool x_apply = ((x_flags & GLAMR_EXT_APPLY_WORLD_RES) || (x_var & GLAMR_EXT_VAR_WORLD_RES)) && !has_wd;      // (:459-465 overwrites both from the base)
+  const int x_TB = x_on ? uni(sx->TB) : 0;
+  float* const x_res = x_on ? glob(sx->res) : nullptr;
+  float* const x_g = x_on ? glob(sx->g) : nullptr;
+  float* const x_ws = x_on ? glob(sx->ws) : nullptr;
+#endif
 
   // A forward pass that is only there for the world poses (GLAMR_FLAG_POSES_ONLY: init_data's pass before init_cam_pose(all_frames), the first
   // launch of every iteration of the launch-by-launch schedules) stops after phase D: it needs neither the visibility tables nor the
@@ -862,6 +905,14 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
     for (int i = rt.tid(); i < l.person_stride; i += rt.nthreads()) sc.ps[p].g[i] = 0.f;
     for (int i = rt.tid(); i < lo.person_stride; i += rt.nthreads()) { sc.ps[p].m[i] = 0.f; sc.ps[p].v[i] = 0.f; }
   }
+#ifdef GLAMR_GRECON_WIDE
+  if constexpr (x_on)      // fresh moments per stage; a frame's rows are only ever touched by the thread that owns the frame
+    for (int p = 0; p < P; ++p)
+      for (int t = rt.tid(); frame_in(t, T); t += rt.nthreads()) {
+        float* w = x_ws + ((size_t)p * x_TB + t) * EXT_WS;
+        for (int k = 0; k < 16; ++k) w[k] = 0.f;
+      }
+#endif
   const int rs = AF ? lo.cam_inv_rot_res : 0;          // index shift of the camera residuals in the on-chip (compact) camera block
   const int Tb = l.cam_trans / 6;                      // frames of the batch layout
   if (AF) {
@@ -1023,6 +1074,9 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
     float lsum[GLAMR_NUM_LOSSES];
     for (int i = 0; i < GLAMR_NUM_LOSSES; ++i) lsum[i] = 0.f;
     float kp_dist_cnt = 0.f;
+#ifdef GLAMR_GRECON_WIDE
+    float xsum[GLAMR_EXT_NUM_LOSSES] = {0.f, 0.f};
+#endif
     GLAMR_MARK_BEGIN(rt);
 
     // ---- A: heading increments (arrays are indexed by VIDEO frame t and zero outside the person's existing range, so the
@@ -1142,6 +1196,26 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
         float w1[3], w2[3];
         rotz2(cs, sn, c1, w1);
         rotz2(cs, sn, c2, w2);
+#ifdef GLAMR_GRECON_WIDE
+        // world_res (:452-454): orient = angle-axis(R_w) + res, trans += res -- then world_dxy (:467-468), on every frame of the scene
+        float x_aa[3] = {0.f, 0.f, 0.f};
+        if constexpr (x_on) if (!frozen) {
+          const size_t xi = (size_t)p * x_TB + t;
+          const float* xr = x_res + xi * GLAMR_EXT_FLOATS;
+          if (x_apply) {
+            float* xw = x_ws + xi * EXT_WS;
+            const float pre[6] = {w1[0], w1[1], w1[2], w2[0], w2[1], w2[2]};
+            for (int k = 0; k < 6; ++k) xw[16 + k] = pre[k];
+            float Rw[9], R2[9];
+            cols_to_R(pre, Rw);
+            rm::rotmat_to_aa(Rw, x_aa);
+            for (int k = 0; k < 3; ++k) x_aa[k] += xr[2 + k];
+            rm::aa_to_rotmat_k(x_aa, R2);
+            for (int k = 0; k < 3; ++k) { w1[k] = R2[k * 3 + 0]; w2[k] = R2[k * 3 + 1]; tb[k] += xr[5 + k]; }
+          }
+          if (x_has_dxy) { tb[0] += xr[0]; tb[1] += xr[1]; }
+        }
+#endif
         s.Lc[10 * sh.TM + t] = cs;
         s.Lc[11 * sh.TM + t] = sn;
         for (int k = 0; k < 3; ++k) {
@@ -1155,6 +1229,9 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
           rm::rotmat_to_aa(Rw, ow);
           for (int k = 0; k < 3; ++k) { s.orient_world[t * 3 + k] = ow[k]; s.trans_world[t * 3 + k] = tb[k]; }
         }
+#ifdef GLAMR_GRECON_WIDE
+        if constexpr (x_on) if (last && x_apply && !frozen) for (int k = 0; k < 3; ++k) s.orient_world[t * 3 + k] = x_aa[k];      // the sum itself, as the reference reports it
+#endif
       }
       // ---- D: camera of this frame, unless it is derived from the persons (needs other frames' transforms) -----------------
       if (!cam_from_person) {
@@ -1666,6 +1743,56 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
         // R_w = Rz(phi) [b2 b3 | .]:  d/dphi = J R_w with J = [[0,-1,0],[1,0,0],[0,0,0]]
         const float* d6 = s.d6 + t * 6;
         const float* g6 = s.g_d6 + t * 6;
+#ifdef GLAMR_GRECON_WIDE
+        // reverse of the residual step, the regularisers and Adam on the residuals (own frame only); with world_res applied the adjoint of the
+        // rotation columns goes back through aa -> R (aa_to_rotmat_k) and R_w -> aa (rotmat_to_aa) onto the columns the chain below made
+        float x_d6[6], x_g6[6];
+        if constexpr (x_on) if (!(!SINGLE && c.frozen)) {
+          const size_t xi = (size_t)p * x_TB + t;
+          float* xr = x_res + xi * GLAMR_EXT_FLOATS;
+          float* xw = x_ws + xi * EXT_WS;
+          const bool upd_dxy = update && (x_var & GLAMR_EXT_VAR_WORLD_DXY), upd_res = update && (x_var & GLAMR_EXT_VAR_WORLD_RES);
+          AdamRegs<2> a_dxy;
+          AdamRegs<6> a_res;
+          a_dxy.zero(); a_res.zero();
+          if (upd_dxy) a_dxy.load(xr, xw, xw + 8, 0); else for (int k = 0; k < 2; ++k) a_dxy.P[k] = xr[k];
+          if (upd_res) a_res.load(xr, xw, xw + 8, 2); else for (int k = 0; k < 6; ++k) a_res.P[k] = xr[2 + k];
+          float gd[2] = {0.f, 0.f}, gr[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+          if (x_has_dxy) { gd[0] = s.g_tw[t * 3 + 0]; gd[1] = s.g_tw[t * 3 + 1]; }
+          if (x_apply) {
+            for (int k = 0; k < 3; ++k) gr[3 + k] = s.g_tw[t * 3 + k];
+            for (int k = 0; k < 6; ++k) x_d6[k] = xw[16 + k];
+            float Rw[9], aa[3], gR2[9], gaa[3] = {0.f, 0.f, 0.f}, gRw[9];
+            cols_to_R(x_d6, Rw);
+            rm::rotmat_to_aa(Rw, aa);
+            for (int k = 0; k < 3; ++k) aa[k] += a_res.P[k];
+            for (int r = 0; r < 3; ++r) { gR2[r * 3 + 0] = g6[r]; gR2[r * 3 + 1] = g6[3 + r]; gR2[r * 3 + 2] = 0.f; }      // (the third column's is folded onto these two)
+            rm::aa_to_rotmat_k_bwd(aa, gR2, gaa);
+            for (int k = 0; k < 3; ++k) gr[k] = gaa[k];
+            for (int k = 0; k < 9; ++k) gRw[k] = 0.f;
+            rm::rotmat_to_aa_bwd(Rw, gaa, gRw);
+            fold_R_grad(x_d6, gRw, x_g6);
+            d6 = x_d6; g6 = x_g6;
+          }
+          const float n_x = (float)(P * T);
+          for (int i = 0; i < GLAMR_EXT_NUM_LOSSES; ++i) {
+            if (!((x_lmask >> i) & 1u)) continue;
+            const float w = ((x_mon >> i) & 1u) ? 0.f : sx->weight[i] / n_x;
+            for (int k = 0; k < 3; ++k) {
+              const float r = a_res.P[i * 3 + k] * FPS;
+              if (last) xsum[i] += r * r;
+              gr[i * 3 + k] += 2.0f * FPS * r * w;
+            }
+          }
+          if (upd_dxy || upd_res) adam_step2(a_dxy, gd, a_res, gr, ac);
+          if (upd_dxy) a_dxy.store(xr, xw, xw + 8, nullptr, 0, gd);
+          if (upd_res) a_res.store(xr, xw, xw + 8, nullptr, 2, gr);
+          if (x_g) {
+            for (int k = 0; k < 2; ++k) x_g[xi * GLAMR_EXT_FLOATS + k] = gd[k];
+            for (int k = 0; k < 6; ++k) x_g[xi * GLAMR_EXT_FLOATS + 2 + k] = gr[k];
+          }
+        }
+#endif
         const float gphi = (g6[1] * d6[0] - g6[0] * d6[1]) + (g6[4] * d6[3] - g6[3] * d6[4]);
         const float gw[1] = {gphi};
         if (!ex) {
@@ -1882,6 +2009,13 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
         o[GLAMR_LOSS_CAM_ORIGIN_SMOOTHNESS] = tot[GLAMR_LOSS_CAM_ORIGIN_SMOOTHNESS] / (float)(T - 1);
         o[GLAMR_LOSS_CAM_UP_REG] = tot[GLAMR_LOSS_CAM_UP_REG] / n_up;
       }
+#ifdef GLAMR_GRECON_WIDE
+      if constexpr (x_on) {
+        float xt[GLAMR_EXT_NUM_LOSSES];
+        for (int i = 0; i < GLAMR_EXT_NUM_LOSSES; ++i) xt[i] = rt.reduce_sum(xsum[i]);
+        if (rt.tid() == 0) for (int i = 0; i < GLAMR_EXT_NUM_LOSSES; ++i) glob(sx->losses)[i] = xt[i] / (float)(P * T);
+      }
+#endif
     }
     GLAMR_MARK(rt, 8);
   };
@@ -1890,6 +2024,10 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
   float* const hist = FAST == 0 ? uni(sc.loss_history) : nullptr;
   auto keep_losses = [&](int it) {
     if (FAST == 0 && hist && rt.tid() == 0) for (int k = 0; k < GLAMR_NUM_LOSSES; ++k) glob(hist)[(size_t)it * GLAMR_NUM_LOSSES + k] = sh.losses[k];
+#ifdef GLAMR_GRECON_WIDE
+    if constexpr (x_on) if (FAST == 0 && hist && sx->hist && rt.tid() == 0)
+      for (int k = 0; k < GLAMR_EXT_NUM_LOSSES; ++k) glob(sx->hist)[(size_t)it * GLAMR_EXT_NUM_LOSSES + k] = glob(sx->losses)[k];
+#endif
   };
   // GLAMR_FLAG_NO_REPORT (launch-by-launch schedules: the gradient launch of every iteration but a stage's last): the final evaluation is an
   // update-only one as well -- no outputs, no loss values, gradients (and grads_out) as always.  Same two instantiations, one call site each.

@@ -319,6 +319,21 @@ class GlobalReconOptimizer:
         packing.check_penetration(self.opt_stage_specs, self.specs)
         packing.check_aux(self.opt_stage_specs, self.specs)
         self.opt_stage_specs, self._pen_cfg, self._aux_cfg = packing.split_off_kernel(self.opt_stage_specs)
+        # world-frame residuals: `world_dxy` / `world_res` in opt_variables, traj_rot_res / traj_trans_res in loss_cfg.  Their names are
+        # taken off every stage here (what every schedule and stage_desc see is the rest) and run_schedule launches those stages with a
+        # glamr_stage_ext beside the descriptor (glamr_grecon_run_stage_ext: the instances of csrc/grecon_wide.hip).  world_loss_history[stage]:
+        # (scenes, iterations, 2) UNWEIGHTED values, with a log / keep_loss_history.  Without one of the names in any stage nothing changes.
+        self.opt_stage_specs, self._world_cfg = packing.split_world_specs(self.opt_stage_specs)
+        self.world_loss_history = {}
+        if self._world_cfg:
+            what = 'world_dxy / world_res / traj_rot_res / traj_trans_res (the world-frame residuals)'
+            # (the two VJP kernels and glamr_grecon_aux_step do not know the residuals; the other schedules make their own iterations without them)
+            for on, other in ((bool(self._pen_cfg), 'the penetration term (loss_cfg)'), (bool(self._aux_cfg), self._aux_what() if self._aux_cfg else ''),
+                              (bool(g('flag_aux_on_device', False)), 'flag_aux_on_device'),
+                              (bool(g('flag_opt_motion_latent', False) or g('flag_opt_traj_latent', False)), 'the latent-optimisation mode'),
+                              (self.flag_opt_vis_local_rot, 'flag_opt_vis_local_rot'), (bool(g('absolute_heading', False)), 'absolute_heading')):
+                if on:
+                    raise NotImplementedError('%s together with %s is not supported' % (what, other))
         if self._off_kernel_term() is not None:
             extra_loss_schedule.check_supported(self.specs, what=self._off_kernel_term())
         elif self._aux_on_device():
@@ -346,6 +361,9 @@ class GlobalReconOptimizer:
         if fn is not None:
             if not callable(fn):
                 raise TypeError('extra_loss must be callable: extra_loss(ctx) -> tensor (S,)')
+            if getattr(self, '_world_cfg', None):
+                raise NotImplementedError('extra_loss together with world_dxy / world_res / traj_rot_res / traj_trans_res (the world-frame residuals) is not '
+                                          'supported: glamr_grecon_pose_backward does not know the residuals')
             extra_loss_schedule.check_supported(self.specs)
         self._extra_loss = fn
 
@@ -377,6 +395,11 @@ class GlobalReconOptimizer:
             raise NotImplementedError('%s %s (optimize / optimize_batch only)' % (what, why))
 
     def _run_schedule_or_extra(self, packed, max_iters, has_wd=False):
+        if packed.has_world_dxy and (self._aux_on_device() or self._off_kernel_term() is not None):
+            # (a continued optimisation of a result that carries world_dxy: the reference adds it on every frame of every later stage, :467-468,
+            # and the launch-by-launch schedules do not know it)
+            raise NotImplementedError('an existing world_dxy (the world-frame residuals) together with %s is not supported'
+                                      % ('the loss_cfg terms of glamr_grecon_aux_step' if self._aux_on_device() else self._off_kernel_term()))
         if self._aux_on_device():
             return aux_step_schedule.AuxStepSchedule(self, packed).run(max_iters, has_wd=has_wd)
         if self._off_kernel_term() is None:
@@ -919,6 +942,8 @@ class GlobalReconOptimizer:
         src.update({'pa_' + k: v for k, v in packed.person_arrays.items() if k not in ('nets_pose', 'nets_vis')})
         if 'rel_transform_cam' in packed.t:
             src['rel'] = packed.t['rel_transform_cam']
+        if 'world_res' in packed.t:
+            src['world_res'] = packed.t['world_res']
         ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
         host = {}
         rin = packed.keepalive[0] if packed.keepalive else None
@@ -959,7 +984,9 @@ class GlobalReconOptimizer:
             return out
         fr_start, fr_end = h['fr_start'].tolist(), h['fr_end'].tolist()
         wd = 'world_dheading' in stage_vars
-        person_keys = _PERSON_KEYS + (('world_dheading',) if wd else ())
+        # the world-frame residuals: world_dxy once created, the residual tensors once a stage listed world_res or one of their terms
+        world_keys = tuple(k for k in packing.WORLD_KEYS if 'world_res' in h and (packed.has_world_dxy if k == 'world_dxy' else packed.world_res_listed))
+        person_keys = _PERSON_KEYS + (('world_dheading',) if wd else ()) + world_keys
 
         def person_factory(k, pi, si, Ts):
             fs, fe = fr_start[k], fr_end[k]
@@ -967,6 +994,7 @@ class GlobalReconOptimizer:
             frame = lambda name: (lambda: h[name][k, :Ts])
             var = lambda name: (lambda: packing.person_view(h['params'][si], l, pi, name)[packing.var_rows(name, n, Ts)])
             cut = {name: var(name) for name in packing.PERSON_VARS}
+            cut.update({key: (lambda key=key: h['world_res'][k, :Ts, packing.WORLD_KEYS[key]]) for key in world_keys})
             cut.update({
                 'smpl_pose': frame('pa_smpl_pose'), 'smpl_beta': frame('pa_smpl_beta'), 'smpl_orient_cam': frame('orient_cam'), 'root_trans_cam': frame('pa_trans_cam'),
                 'cam_K': lambda: h['cam_K'][k, :Ts].reshape(Ts, 3, 3), 'traj_local_pred': lambda: h['traj_local_pred'][k, :n],
@@ -1073,31 +1101,46 @@ class GlobalReconOptimizer:
             sd = packing.stage_desc(spec, self.specs, has_world_dheading=has_wd, niters=stepwise.stage_iters(spec, max_iters))
             if want_hist and sd.niters > 0:
                 packed.t['loss_history'] = torch.zeros((packed.S, int(sd.niters), len(packing.LOSS_IDS)), dtype=torch.float32, device=self.device)
-            events.append(self._run(packed, sd))               # the launch's workspace: its header carries the kernel's own clock stamps
+            world = stepwise.world_stage(packed, self._world_cfg.get(stage))
+            if world is None:
+                events.append(self._run(packed, sd))               # the launch's workspace: its header carries the kernel's own clock stamps
+                whist = None
+            else:
+                if packed.t.get('frozen') is not None:
+                    raise NotImplementedError('world_dxy / world_res / traj_rot_res / traj_trans_res (the world-frame residuals) on a person-sharded batch')
+                ext, keep = packing.world_ext(world, packed, niters=int(sd.niters), want_hist='loss_history' in packed.t)
+                stepwise.run_stage(packed, sd, False, ext=ext)
+                events.append(packed.last_ws)
+                stepwise.end_world_stage(packed, world, keep)
+                whist = keep.get('loss_history')
             if 'loss_history' in packed.t:
-                self._report_stage(packed, stage, spec, packed.t.pop('loss_history'), events[-1])
+                self._report_stage(packed, stage, spec, packed.t.pop('loss_history'), events[-1], whist, (world or {}).get('loss_order'))
             has_wd = stepwise.end_stage(packed, spec, has_wd)
         packed.has_world_dheading = has_wd
         packed.stage_ws = events
         return packed
 
-    def _report_stage(self, packed, stage, spec, hist, ws):
+    def _report_stage(self, packed, stage, spec, hist, ws, world_hist=None, loss_order=None):
         """write_logs (:646-659) for every iteration of a finished stage launch: `cfg id - sequence - stage | it/niters | TE: .. ETA: .. | LR: .. |
         term: value | ...` with the UNWEIGHTED values (loss_uw_dict, :564) of the stage's terms in the order of its loss_cfg.  The time per
         iteration is the launch's duration divided by its iterations."""
         import datetime
         h = hist.cpu().numpy()                                          # (waits for the launch)
         self.loss_history[stage] = h
+        wh = world_hist.cpu().numpy() if world_hist is not None else None
+        if wh is not None:
+            self.world_loss_history[stage] = wh
         if self.log is None:
             return
         n_it = h.shape[1]
         it_secs = self.launch_ms(ws) * 1e-3 / max(1, n_it)
         hms = lambda secs: str(datetime.timedelta(seconds=round(secs)))
-        names = [n for n in spec['loss_cfg'] if n in packing.LOSS_IDS]
+        names = [n for n in (loss_order or spec['loss_cfg']) if n in packing.LOSS_IDS or (wh is not None and n in packing.WORLD_TERMS)]
+        value = lambda si, it, n: h[si, it, packing.LOSS_IDS[n]] if n in packing.LOSS_IDS else wh[si, it, packing.WORLD_TERMS[n]]
         for si in range(packed.S):
             head = '%s - %s - %s' % (self.cfg_id, packed.seq_names[si], stage)
             for it in range(n_it):
-                loss_str = ' | '.join('%s: %7.3f' % (n, h[si, it, packing.LOSS_IDS[n]]) for n in names)
+                loss_str = ' | '.join('%s: %7.3f' % (n, value(si, it, n)) for n in names)
                 self.log.info('%s | %4d/%d | TE: %s ETA: %s | LR: %.0e | %s' % (head, it, n_it, hms(it_secs), hms(it_secs * (n_it - it - 1)), spec['opt_lr'], loss_str))
 
     def _run_schedule_masked(self, packed, max_iters, has_wd):

@@ -118,6 +118,82 @@ def split_off_kernel(opt_stage_specs):
     return (rest_specs if pen_cfg or aux_cfg else opt_stage_specs), pen_cfg, aux_cfg
 
 
+# World-frame residuals: the variables `world_dxy` / `world_res` (global_recon_model.py:452-454, 467-468, 611-613, 628-631) and their
+# regularisers (loss_func.py:189-209), in the order of glamr_stage_ext's bits.  Not part of glamr_stage_desc either (stage_desc refuses all
+# four names): split_world takes them off a stage and world_ext makes the glamr_stage_ext that glamr_grecon_run_stage_ext runs beside it.
+WORLD_VARS = {'world_dxy': 1, 'world_res': 2}                     # GLAMR_EXT_VAR_*
+WORLD_TERMS = {'traj_rot_res': 0, 'traj_trans_res': 1}            # GLAMR_EXT_LOSS_*
+EXT_HAS_WORLD_DXY, EXT_APPLY_WORLD_RES = 1, 2
+EXT_FLOATS, EXT_WS_FLOATS = 8, 24                                 # per slot and frame: world_dxy 0-1, smpl_orient_world_res 2-4, root_trans_world_res 5-7
+WORLD_KEYS = {'world_dxy': slice(0, 2), 'smpl_orient_world_res': slice(2, 5), 'root_trans_world_res': slice(5, 8)}      # pose_dict key -> columns
+
+
+def split_world(spec):
+    """A stage's spec -> (the spec stage_desc is given: without the names of WORLD_VARS and WORLD_TERMS -- the argument itself when it lists
+    none --, None or dict(variables=[names of WORLD_VARS in the stage's order], terms={name: dict(weight, monitor_only)} in loss_cfg's order,
+    loss_order=[every name of the stage's loss_cfg]))."""
+    variables = [v for v in spec['opt_variables'] if v in WORLD_VARS]
+    terms = {n: dict(weight=float(c['weight']), monitor_only=bool(c.get('monitor_only', False))) for n, c in spec['loss_cfg'].items() if n in WORLD_TERMS}
+    if not variables and not terms:
+        return spec, None
+    rest = dict(spec, opt_variables=[v for v in spec['opt_variables'] if v not in WORLD_VARS],
+                loss_cfg={n: c for n, c in spec['loss_cfg'].items() if n not in WORLD_TERMS})
+    world = dict(variables=variables, terms=terms, loss_order=list(spec['loss_cfg']))
+    rest['world_residuals'] = world      # (a schedule that is handed the stripped specs and cannot run the residuals sees that they were there: has_world)
+    return rest, world
+
+
+def has_world(opt_stage_specs):
+    """Whether a schedule lists a world-frame residual's name, in its stages or taken off them by split_world."""
+    return any(spec.get('world_residuals') or split_world(spec)[1] for spec in opt_stage_specs.values())
+
+
+def split_world_specs(opt_stage_specs):
+    """opt_stage_specs -> (the specs without the world-frame residuals' names -- the argument itself when no stage lists one --, {stage:
+    split_world's second result} for the stages that do)."""
+    rest, world = {}, {}
+    for stage, spec in opt_stage_specs.items():
+        rest[stage], w = split_world(spec)
+        if w is not None:
+            world[stage] = w
+    return (rest if world else opt_stage_specs), world
+
+
+def world_ext(world, packed, niters=0, want_grads=False, want_hist=False):
+    """split_world's second result (or None: a stage that only carries an existing world_dxy along) -> glamr_stage_ext on `packed`'s residual
+    arrays (packed.world_arrays makes them), and the tensors it points at beside the residuals: dict(losses, ws[, grads][, loss_history])."""
+    world = world or dict(variables=[], terms={})
+    ex = _lib.StageExt()
+    ex.var_mask = 0
+    for v in world['variables']:
+        ex.var_mask |= WORLD_VARS[v]
+    ex.flags = (EXT_HAS_WORLD_DXY if packed.has_world_dxy else 0) | (EXT_APPLY_WORLD_RES if 'world_res' in world['variables'] else 0)
+    ex.loss_mask = ex.monitor_mask = 0
+    for i in range(len(WORLD_TERMS)):
+        ex.loss_weight[i] = 0.0
+    for name, c in world['terms'].items():
+        i = WORLD_TERMS[name]
+        ex.loss_mask |= 1 << i
+        ex.loss_weight[i] = c['weight']
+        if c['monitor_only']:
+            ex.monitor_mask |= 1 << i
+    res = packed.world_arrays()
+    dev, S = res.device, packed.S
+    ws_floats = _lib.lib().glamr_grecon_ext_workspace_bytes(S, packed.P, packed.T) // 4      # (the library sizes it: EXT_WS_FLOATS per slot and frame)
+    assert ws_floats == res.shape[0] * res.shape[1] * EXT_WS_FLOATS, 'glamr_grecon_ext_workspace_bytes and packing.EXT_WS_FLOATS disagree'
+    keep = dict(losses=torch.zeros((S, len(WORLD_TERMS)), dtype=torch.float32, device=dev),
+                ws=torch.empty(ws_floats, dtype=torch.float32, device=dev).view(res.shape[:2] + (EXT_WS_FLOATS,)))
+    if want_grads:
+        keep['grads'] = torch.zeros_like(res)
+    if want_hist and niters > 0:
+        keep['loss_history'] = torch.zeros((S, int(niters), len(WORLD_TERMS)), dtype=torch.float32, device=dev)
+    ex.residuals = ctypes.c_void_p(res.data_ptr())
+    for name in ('losses', 'grads', 'loss_history'):
+        setattr(ex, name, ctypes.c_void_p(keep[name].data_ptr()) if name in keep else None)
+    ex.workspace = ctypes.c_void_p(keep['ws'].data_ptr())
+    return ex, keep
+
+
 def aux_desc(aux_cfg):
     """split_aux's second result -> glamr_aux_desc."""
     ad = _lib.AuxDesc()
@@ -284,6 +360,16 @@ class PackedScenes:
         self.root_trans_cam = None      # (S * P, T, 3) the persons' pd['root_trans_cam'] of a batch packed from host dictionaries (cam_traj_trans reads it)
         self.stage_ws = []
         self.aux_values = None          # {stage: (S, iterations, 6)} on the device: aux_step_schedule.AuxStepSchedule's values of the last schedule (collect() publishes them)
+        # world-frame residuals (split_world / world_ext): t['world_res'] (S * P, T, 8) exists once a stage needs it (world_arrays); `world_dxy` exists
+        # from the first stage that lists it on, like has_world_dheading; the residual tensors are reported once a stage listed world_res or a term
+        self.has_world_dxy = self.world_res_listed = False
+        self.world_losses = None        # (S, 2) on the device: traj_rot_res, traj_trans_res of the last stage that ran with the extension
+
+    def world_arrays(self):
+        """t['world_res']: (S * P, T, 8) world_dxy | smpl_orient_world_res | root_trans_world_res by video frame, zeros when first asked for."""
+        if 'world_res' not in self.t:
+            self.t['world_res'] = torch.zeros((self.S * self.P, self.T, EXT_FLOATS), dtype=torch.float32, device=self.device)
+        return self.t['world_res']
 
     @classmethod
     def empty(cls, n_scenes, max_persons, max_len, device, with_rel=None, seq_names=None):
@@ -335,6 +421,8 @@ class PackedScenes:
         cpu = lambda x: torch.as_tensor(x).detach().to('cpu')
         l = self.layout
         rtc = f32(S * P, T, 3) if all('root_trans_cam' in pd for d in datas for pd in d['person_data'].values()) else None
+        # a continued optimisation resumes from the world-frame residuals an earlier run returned (world_dxy exists from then on)
+        world = f32(S * P, T, EXT_FLOATS) if any(k in pd for d in datas for pd in d['person_data'].values() for k in WORLD_KEYS) else None
         for si, d in enumerate(datas):
             ids = self.person_ids[si]
             Ts = int(d['seq_len'])
@@ -367,6 +455,9 @@ class PackedScenes:
                 t['person2cam'][slot, :Ts] = cpu(pd['person2cam'])[:, :3, :].reshape(Ts, 12).float()
                 if rtc is not None:
                     rtc[slot, :Ts] = cpu(pd['root_trans_cam']).float()
+                for key, cols in WORLD_KEYS.items():
+                    if key in pd:
+                        world[slot, :Ts, cols] = cpu(pd[key]).float()
                 if need_mask:
                     m = torch.ones(n - 1)
                     for (s, e) in cam_fix_frames:
@@ -390,6 +481,10 @@ class PackedScenes:
                 jl[si * P + pi, :int(d['seq_len'])] = j_locals[si][idx] if on_device else cpu(j_locals[si][idx]).float()
         self.t['j_local'] = jl if on_device else jl.contiguous().to(device)
         self.has_world_dheading = any('world_dheading' in pd for d in datas for pd in d['person_data'].values())
+        if world is not None:
+            self.t['world_res'] = world.to(device)
+            self.has_world_dxy = any('world_dxy' in pd for d in datas for pd in d['person_data'].values())
+            self.world_res_listed = any('smpl_orient_world_res' in pd for d in datas for pd in d['person_data'].values())
 
     def struct(self):
         sb = _lib.SceneBatch()
@@ -419,6 +514,8 @@ class PackedScenes:
         tensor names the reference uses (global_recon_model.py:396-426,459-480,512-528,598-606)."""
         l, P = self.layout, self.P
         h = self.fetch()
+        world = self.t['world_res'].detach().cpu().numpy() if 'world_res' in self.t else None
+        world_keys = [k for k in WORLD_KEYS if world is not None and (self.has_world_dxy if k == 'world_dxy' else self.world_res_listed)]
         conv = (lambda a: torch.from_numpy(np.ascontiguousarray(a))) if as_torch else (lambda a: np.ascontiguousarray(a))
         var = set(stage_specs['opt_variables']) if stage_specs is not None else set()
         for si, d in enumerate(datas):
@@ -445,6 +542,8 @@ class PackedScenes:
                 for name in PERSON_VARS:
                     if name != 'world_dheading' or name in var or name in pd:
                         pd[name] = conv(person_view(prm, l, pi, name)[var_rows(name, n, Ts)])
+                for key in world_keys:
+                    pd[key] = conv(world[slot, :Ts, WORLD_KEYS[key]])
                 pd['smpl_orient_world'] = conv(h['orient_world'][slot, :Ts])
                 pd['root_trans_world'] = conv(h['trans_world'][slot, :Ts])
                 pd['kp_2d_pred'] = conv(h['kp_2d_pred'][slot, :Ts])

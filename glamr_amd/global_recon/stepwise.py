@@ -33,15 +33,35 @@ def grad_launch_desc(spec, model_specs, has_wd, first, extra_flags=0):
     return sd
 
 
-def run_stage(packed, sd, want_grads, ws=None):
+def world_stage(packed, world):
+    """What a stage's launch takes of the world-frame residuals: `world` (packing.split_world's second result for the stage, or None) when the
+    stage lists one of their names, {} when it only carries an existing world_dxy along (:467-468 adds it in every later stage), None when the
+    plain launch serves the stage."""
+    return world if world is not None else ({} if packed.has_world_dxy else None)
+
+
+def end_world_stage(packed, world, keep):
+    """After a stage that ran with the extension: `world_dxy` exists from the first stage that lists it on (get_parameter :628-631), the residual
+    tensors are reported once a stage listed world_res or one of the terms, and the two terms' last values stay with the batch."""
+    if world:
+        packed.has_world_dxy = packed.has_world_dxy or 'world_dxy' in world['variables']
+        packed.world_res_listed = packed.world_res_listed or 'world_res' in world['variables'] or bool(world['terms'])
+    packed.world_losses = keep['losses']
+
+
+def run_stage(packed, sd, want_grads, ws=None, ext=None):
     """glamr_grecon_run_stage on the packed batch (current stream); returns the gradient record (n_scenes, scene_stride) or None.  `ws`: a
-    workspace the caller keeps across launches (GLAMR_FLAG_KEEP_TABLES needs the previous launch's); a fresh one otherwise (packed.last_ws)."""
+    workspace the caller keeps across launches (GLAMR_FLAG_KEEP_TABLES needs the previous launch's); a fresh one otherwise (packed.last_ws).
+    `ext`: a glamr_stage_ext (packing.world_ext) -- the launch then is glamr_grecon_run_stage_ext's."""
     L = _lib.lib()
     sb = packed.struct()
     grads = torch.zeros_like(packed.t['params']) if want_grads else None
     if ws is None:
         ws = torch.empty(L.glamr_grecon_workspace_bytes(packed.S, packed.P, packed.T), dtype=torch.uint8, device=packed.device)
-    _lib.check(L.glamr_grecon_run_stage(ctypes.byref(sb), ctypes.byref(sd), _lib.ptr(grads), _lib.ptr(ws), _lib.current_stream()))
+    if ext is None:
+        _lib.check(L.glamr_grecon_run_stage(ctypes.byref(sb), ctypes.byref(sd), _lib.ptr(grads), _lib.ptr(ws), _lib.current_stream()))
+    else:
+        _lib.check(L.glamr_grecon_run_stage_ext(ctypes.byref(sb), ctypes.byref(sd), ctypes.byref(ext), _lib.ptr(grads), _lib.ptr(ws), _lib.current_stream()))
     packed.last_ws = ws
     return grads
 

@@ -189,6 +189,9 @@ class PersonShardedSchedule:
         S, P, T, l = packed.S, packed.P, packed.T, packed.layout
         if P < self.world:
             raise ValueError('%d persons cannot be sharded over %d ranks' % (P, self.world))
+        if packing.has_world(opt_stage_specs) or getattr(packed, 'has_world_dxy', False):      # (a model's opt_stage_specs have the names taken off and say so)
+            raise NotImplementedError('world_dxy / world_res / traj_rot_res / traj_trans_res (the world-frame residuals) in a person-sharded run is not '
+                                      'supported: the schedule makes its own Adam steps on `params`, which does not hold them')
         own = self.owned(P)
         block = -(-P // self.world)
         frozen = torch.ones((S, P), dtype=torch.int32)

@@ -394,6 +394,41 @@ size_t glamr_grecon_workspace_bytes(int n_scenes, int max_persons, int max_len);
  * If `grads_out` (dev, n_scenes*scene_stride) is non-NULL the gradient of the LAST evaluated iteration is stored there. */
 int glamr_grecon_run_stage(const glamr_scene_batch* batch, const glamr_stage_desc* stage, float* grads_out,
                            void* workspace, void* stream);
+/* World-frame residuals: the variables `world_dxy` and `world_res` of the reference (global_recon_model.py:176-177, 452-454, 467-468, 611-613,
+ * 628-631) and their regularisers traj_rot_res / traj_trans_res (loss_func.py:189-209), applied to the world poses after
+ * get_pred_trajectory_base.  Per person slot and VIDEO frame t, 8 floats: world_dxy (2), smpl_orient_world_res (3), root_trans_world_res (3).
+ *   GLAMR_EXT_HAS_WORLD_DXY: pose_dict['world_dxy'] exists (this or an earlier stage listed it): root_trans_world[:, :2] += world_dxy on every
+ *     frame of the scene (:467-468), last.
+ *   GLAMR_EXT_APPLY_WORLD_RES: the stage lists `world_res` (:452-454): orient = angle-axis(R_w) + res, trans += res.  With a world heading offset
+ *     (GLAMR_FLAG_HAS_WORLD_DHEADING or GLAMR_VAR_WORLD_DHEADING) the reference overwrites both from the base (:459-465): the residuals are then
+ *     not applied and receive no data gradient.
+ *   var_mask: what the stage's Adam updates (fresh zero moments per launch), frames t < seq_len of the slots p < n_persons only; arrays beyond
+ *     are never read or written.  Frozen slots (glamr_scene_batch.frozen) are refused.
+ *   loss_mask / monitor_mask / loss_weight: bit and index GLAMR_EXT_LOSS_*; value = sum_persons sum (30 x)^2 / sum_persons seq_len.  Their
+ *     gradient reaches the residuals only where GLAMR_EXT_VAR_WORLD_RES is set.
+ * A non-NULL `ext` runs on the instances of csrc/grecon_wide.hip whatever the person count (every other instance is compiled without it);
+ * glamr_grecon_run_stage is this call with ext == NULL.  Not with g_traj_local. */
+#define GLAMR_EXT_VAR_WORLD_DXY (1u << 0)
+#define GLAMR_EXT_VAR_WORLD_RES (1u << 1)
+#define GLAMR_EXT_HAS_WORLD_DXY (1u << 0)
+#define GLAMR_EXT_APPLY_WORLD_RES (1u << 1)
+enum { GLAMR_EXT_LOSS_TRAJ_ROT_RES = 0, GLAMR_EXT_LOSS_TRAJ_TRANS_RES, GLAMR_EXT_NUM_LOSSES };
+#define GLAMR_EXT_FLOATS 8               /* per slot and frame: world_dxy 0-1, smpl_orient_world_res 2-4, root_trans_world_res 5-7 */
+typedef struct glamr_stage_ext {
+  uint32_t var_mask;                     /* GLAMR_EXT_VAR_* */
+  uint32_t flags;                        /* GLAMR_EXT_HAS_WORLD_DXY | GLAMR_EXT_APPLY_WORLD_RES */
+  uint32_t loss_mask, monitor_mask;      /* bit GLAMR_EXT_LOSS_* */
+  float loss_weight[GLAMR_EXT_NUM_LOSSES];
+  float* residuals;                      /* dev (slots, max_len, GLAMR_EXT_FLOATS) in/out */
+  float* grads;                          /* dev, same shape, or NULL: the gradient of the LAST evaluated iteration (the variables the stage does
+                                            not optimise: what it would be) */
+  float* losses;                         /* dev (n_scenes, GLAMR_EXT_NUM_LOSSES) unweighted values of the LAST evaluation (a term not in loss_mask: 0) */
+  float* loss_history;                   /* dev (n_scenes, stage->niters, GLAMR_EXT_NUM_LOSSES) or NULL; read only when batch->loss_history is recorded */
+  void* workspace;                       /* dev, glamr_grecon_ext_workspace_bytes: Adam moments and the pose before the residual */
+} glamr_stage_ext;
+size_t glamr_grecon_ext_workspace_bytes(int n_scenes, int max_persons, int max_len);
+int glamr_grecon_run_stage_ext(const glamr_scene_batch* batch, const glamr_stage_desc* stage, const glamr_stage_ext* ext, float* grads_out,
+                               void* workspace, void* stream);
 /* Duration of the last glamr_grecon_run_stage that used `workspace`, from the kernel's own clock (earliest workgroup start to latest
  * workgroup end, 10 ns resolution): what a profiler reports for the dispatch, also when other streams share the GPU.  Blocks until
  * the work enqueued so far on THAT launch's stream has finished -- other streams keep running (no device-wide wait). */
