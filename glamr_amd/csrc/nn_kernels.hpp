@@ -515,6 +515,29 @@ __device__ __forceinline__ void split8(const float (&x)[8], f16x8& hi, f16x8& lo
     lo[i] = (_Float16)(x[i] - (float)h);
   }
 }
+// The same split with the value and its remainder pinned in registers ahead of their conversions.  qkv_attention_kernel splits
+// (acc + bias) * scale with this one.  With split8 the compiler folded the multiply into the conversions there: h = v_fma_mixlo_f16(t, scale, 0),
+// lo = v_fma_mixlo_f16(t, scale, -h) (128 of them, the only ones among the priors' kernels).  On paper that is at least as exact as convert-then-subtract;
+// on the MI355X it left about 8 query rows in 2050 at 3e-5 to 1.2e-4 from fp64 under the large logits of the conditioned checkpoint, the
+// same rows on every call, where the kernels that convert with v_cvt_f16_f32 / v_cvt_pk_f16_f32 are at 5e-7 (tests/test_infiller_gpu.py,
+// DESIGN.md section 3).  SUPPOSED mechanism, not pinned down: the mix instructions treat fp16 subnormals differently (h flushed when
+// |t * scale| < 6.1e-5, or read back as 0 as an fp16 source), so that an element that small is lost or counted twice -- about one Q / K
+// element in 1e5 is, which fits the number of rows and their dependence on the data.  What is measured: with the fold prevented the rows are
+// at 7e-6, the level of the other kernel families.  Only this site gets the pinned form: attention_mfma_kernel and attention_free_kernel
+// scale a value they have just loaded and the compiler does not fold there (their code holds no mix instruction); the fp64 bounds of
+// tests/test_infiller_gpu.py hold every route to 16 roundings and fail if a later compiler folds one of them.
+__device__ __forceinline__ void split8b(const float (&x)[8], f16x8& hi, f16x8& lo) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    float v = x[i];
+    asm volatile("" : "+v"(v));          // the value as it stands in a register: nothing upstream folds into the conversion
+    const _Float16 h = (_Float16)v;
+    float r = v - (float)h;
+    asm volatile("" : "+v"(r));
+    hi[i] = h;
+    lo[i] = (_Float16)r;
+  }
+}
 __device__ __forceinline__ f32x16 mfma3(const f16x8& ah, const f16x8& al, const f16x8& bh, const f16x8& bl, f32x16 acc) {
   acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
@@ -730,7 +753,7 @@ __global__ __launch_bounds__(512, 1) void qkv_attention_kernel(QkvAttnArgs a) {
           const int r = 8 * u + j, dim = (r & 3) + 8 * (r >> 2) + 4 * kg;
           x[j] = (acc[t][r] + (bias ? bias[nb * 32 + dim] : 0.0f)) * scale;
         }
-        split8(x, fh[t][u], fl[t][u]);
+        split8b(x, fh[t][u], fl[t][u]);
       }
     }
   };
@@ -774,7 +797,7 @@ __global__ __launch_bounds__(512, 1) void qkv_attention_kernel(QkvAttnArgs a) {
             const int r = 8 * u + j, dim = (r & 3) + 8 * (r >> 2) + 4 * kg;
             x[j] = (acc[m][t][r] + (bias ? bias[nb * 32 + dim] : 0.0f)) * scale;
           }
-          if (m) split8(x, kh_[t][u], kl_[t][u]); else split8(x, qh_[t][u], ql_[t][u]);
+          if (m) split8b(x, kh_[t][u], kl_[t][u]); else split8b(x, qh_[t][u], ql_[t][u]);
         }
       }
   } else {
