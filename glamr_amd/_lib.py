@@ -32,7 +32,9 @@ class SceneBatch(Structure):
 
 class StageExt(Structure):      # glamr_stage_ext (glamr_grecon_run_stage_ext: world_dxy / world_res and their regularisers)
     _fields_ = [('var_mask', c_uint32), ('flags', c_uint32), ('loss_mask', c_uint32), ('monitor_mask', c_uint32), ('loss_weight', c_float * 2)] + \
-               [(n, c_void_p) for n in ('residuals', 'grads', 'losses', 'loss_history', 'workspace')]
+               [(n, c_void_p) for n in ('residuals', 'grads', 'losses', 'loss_history', 'workspace')] + \
+               [(n, c_void_p) for n in ('heading_vec', 'heading_vec_grads', 'heading_vec_workspace')] + \
+               [('hv_loss_mask', c_uint32), ('hv_monitor_mask', c_uint32), ('hv_loss_weight', c_float * 2), ('hv_losses', c_void_p), ('hv_loss_history', c_void_p)]      # heading_type = 'vec'; all zero: as without them
 
 
 AUX_NUM_TERMS = 6           # GLAMR_AUX_NUM_TERMS: the terms of glamr_grecon_aux_terms (packing.AUX_LOSS_IDS names them)
@@ -115,6 +117,7 @@ _SIGNATURES = {
     'glamr_grecon_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'glamr_grecon_run_stage': (c_int, [POINTER(SceneBatch), POINTER(StageDesc), c_void_p, c_void_p, c_void_p]),
     'glamr_grecon_ext_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'glamr_grecon_heading_vec_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'glamr_grecon_run_stage_ext': (c_int, [POINTER(SceneBatch), POINTER(StageDesc), POINTER(StageExt), c_void_p, c_void_p, c_void_p]),
     'glamr_grecon_last_launch_ns': (c_int, [c_void_p, POINTER(ctypes.c_double)]),
     'glamr_grecon_pose_backward_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),

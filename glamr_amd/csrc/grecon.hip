@@ -235,6 +235,11 @@ extern "C" size_t glamr_grecon_ext_workspace_bytes(int n_scenes, int max_persons
   if (n_scenes <= 0 || max_persons < 1 || max_persons > WIDE_MAX_PERSONS || max_len < 2) return 0;
   return (size_t)n_scenes * max_persons * max_len * EXT_WS * sizeof(float);
 }
+// per slot and existing row: Adam's two moments of the two numbers of a heading vector (GLAMR_EXT_HV_WS)
+extern "C" size_t glamr_grecon_heading_vec_workspace_bytes(int n_scenes, int max_persons, int max_len) {
+  if (n_scenes <= 0 || max_persons < 1 || max_persons > WIDE_MAX_PERSONS || max_len < 2) return 0;
+  return (size_t)n_scenes * max_persons * max_len * GLAMR_EXT_HV_WS * sizeof(float);
+}
 extern "C" int glamr_grecon_run_stage_ext(const glamr_scene_batch* batch, const glamr_stage_desc* stage, const glamr_stage_ext* ext, float* grads_out,
                                           void* workspace, void* stream_) {
   if (ext) {
@@ -244,6 +249,16 @@ extern "C" int glamr_grecon_run_stage_ext(const glamr_scene_batch* batch, const 
                       !(ext->loss_mask >> GLAMR_EXT_NUM_LOSSES) && !(ext->monitor_mask >> GLAMR_EXT_NUM_LOSSES), "unknown bits in glamr_stage_ext");
     if (batch->frozen) return fail(GLAMR_E_UNSUPPORTED, "glamr_grecon_run_stage_ext: person-sharded batches (glamr_scene_batch.frozen) are not supported with the world-frame residuals");
     if (batch->g_traj_local) return fail(GLAMR_E_UNSUPPORTED, "glamr_grecon_run_stage_ext: g_traj_local is not supported with the world-frame residuals");
+    if (ext->heading_vec) {      // heading_type = 'vec'
+      GLAMR_REQUIRE(ext->heading_vec_workspace, "glamr_stage_ext.heading_vec needs heading_vec_workspace (glamr_grecon_heading_vec_workspace_bytes)");
+      GLAMR_REQUIRE(!(ext->hv_loss_mask >> GLAMR_EXT_HV_NUM_LOSSES) && !(ext->hv_monitor_mask >> GLAMR_EXT_HV_NUM_LOSSES), "unknown bits in glamr_stage_ext.hv_loss_mask / hv_monitor_mask");
+      GLAMR_REQUIRE(!ext->hv_loss_mask || ext->hv_losses, "glamr_stage_ext.hv_loss_mask needs hv_losses");
+      if (stage->flags & GLAMR_FLAG_ABSOLUTE_HEADING)
+        return fail(GLAMR_E_UNSUPPORTED, "glamr_grecon_run_stage_ext: GLAMR_FLAG_ABSOLUTE_HEADING is not supported with vector headings (glamr_stage_ext.heading_vec)");
+      if ((stage->loss_mask >> GLAMR_LOSS_LOCAL_DHEADING_REG_NEW) & 1u)
+        return fail(GLAMR_E_UNSUPPORTED, "glamr_grecon_run_stage_ext: GLAMR_LOSS_LOCAL_DHEADING_REG_NEW reads the scalar heading entries, which are dead with vector "
+                                         "headings: take the bit off and set GLAMR_EXT_HV_LOSS_DHEADING_REG_NEW in glamr_stage_ext.hv_loss_mask");
+    }
   }
   return run_stage_any(batch, stage, ext, grads_out, workspace, stream_);
 }

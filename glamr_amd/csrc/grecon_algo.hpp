@@ -800,6 +800,11 @@ struct SceneExt {
   float weight[GLAMR_EXT_NUM_LOSSES];
   float *res, *g, *ws, *losses, *hist;      // this scene's first slot / row; g, hist or null
   int TB;                                   // frames per slot of those arrays (the batch's max_len)
+  // heading_type = 'vec' (glamr_stage_ext.heading_vec; hv == null: scalar headings, nothing below is read): per slot and EXISTING row e two
+  // floats added to the prior row's (cos, sin) slots before vec_to_heading, Adam's m (2) and v (2) per row in hv_ws
+  float *hv, *hv_g, *hv_ws, *hv_losses, *hv_hist;
+  unsigned hv_lmask, hv_mon;
+  float hv_weight[GLAMR_EXT_HV_NUM_LOSSES];
 };
 GLAMR_HD void bind_ext(SceneExt& x, const glamr_scene_batch& b, const glamr_stage_ext& e, int si, int niters) {
   const size_t row0 = (size_t)si * b.max_persons * b.max_len;
@@ -811,6 +816,14 @@ GLAMR_HD void bind_ext(SceneExt& x, const glamr_scene_batch& b, const glamr_stag
   x.losses = e.losses + (size_t)si * GLAMR_EXT_NUM_LOSSES;
   x.hist = (e.loss_history && b.loss_history && niters > 0) ? e.loss_history + (size_t)si * niters * GLAMR_EXT_NUM_LOSSES : nullptr;
   x.TB = b.max_len;
+  const size_t rows0 = (size_t)si * b.max_persons * b.max_len;
+  x.hv = e.heading_vec ? e.heading_vec + rows0 * 2 : nullptr;
+  x.hv_g = (e.heading_vec && e.heading_vec_grads) ? e.heading_vec_grads + rows0 * 2 : nullptr;
+  x.hv_ws = e.heading_vec ? static_cast<float*>(e.heading_vec_workspace) + rows0 * GLAMR_EXT_HV_WS : nullptr;
+  x.hv_lmask = e.heading_vec ? e.hv_loss_mask : 0u; x.hv_mon = e.heading_vec ? e.hv_monitor_mask : 0u;
+  for (int k = 0; k < GLAMR_EXT_HV_NUM_LOSSES; ++k) x.hv_weight[k] = e.heading_vec ? e.hv_loss_weight[k] : 0.f;
+  x.hv_losses = (e.heading_vec && e.hv_losses) ? e.hv_losses + (size_t)si * GLAMR_EXT_HV_NUM_LOSSES : nullptr;
+  x.hv_hist = (e.heading_vec && e.hv_loss_history && b.loss_history && niters > 0) ? e.hv_loss_history + (size_t)si * niters * GLAMR_EXT_HV_NUM_LOSSES : nullptr;
 }
 #endif
 // EXT: the instance also carries the world-frame residuals (`sx`; csrc/grecon_wide.hip's compile only, kernels of their own).
@@ -869,6 +882,12 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
   float* const x_res = x_on ? glob(sx->res) : nullptr;
   float* const x_g = x_on ? glob(sx->g) : nullptr;
   float* const x_ws = x_on ? glob(sx->ws) : nullptr;
+  // vector headings: ONE uniform flag (the array's presence); off, every branch below is skipped and the instance computes what it did
+  float* const x_hv = x_on ? glob(sx->hv) : nullptr;
+  float* const x_hvg = x_on ? glob(sx->hv_g) : nullptr;
+  float* const x_hvws = x_on ? glob(sx->hv_ws) : nullptr;
+  const bool x_vec = x_hv != nullptr;
+  const unsigned x_hvl = x_vec ? (unsigned)uni((int)sx->hv_lmask) : 0u, x_hvmon = x_vec ? (unsigned)uni((int)sx->hv_mon) : 0u;
 #endif
 
   // A forward pass that is only there for the world poses (GLAMR_FLAG_POSES_ONLY: init_data's pass before init_cam_pose(all_frames), the first
@@ -912,6 +931,15 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
         float* w = x_ws + ((size_t)p * x_TB + t) * EXT_WS;
         for (int k = 0; k < 16; ++k) w[k] = 0.f;
       }
+  if constexpr (x_on) if (x_vec)      // rows are indexed by EXISTING row e = t - fr_start; the thread that owns video frame t owns row e, here as in phases A and J
+    for (int p = 0; p < P; ++p) {
+      const int fs = sc.pc[p].fr_start, fe = sc.pc[p].fr_end;
+      for (int t = rt.tid(); frame_in(t, T); t += rt.nthreads()) {
+        if (t < fs || t >= fe) continue;
+        float* w = x_hvws + ((size_t)p * x_TB + (t - fs)) * GLAMR_EXT_HV_WS;
+        for (int k = 0; k < GLAMR_EXT_HV_WS; ++k) w[k] = 0.f;
+      }
+    }
 #endif
   const int rs = AF ? lo.cam_inv_rot_res : 0;          // index shift of the camera residuals in the on-chip (compact) camera block
   const int Tb = l.cam_trans / 6;                      // frames of the batch layout
@@ -1076,6 +1104,7 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
     float kp_dist_cnt = 0.f;
 #ifdef GLAMR_GRECON_WIDE
     float xsum[GLAMR_EXT_NUM_LOSSES] = {0.f, 0.f};
+    [[maybe_unused]] float hvsum[GLAMR_EXT_HV_NUM_LOSSES] = {0.f, 0.f};
 #endif
     GLAMR_MARK_BEGIN(rt);
 
@@ -1099,6 +1128,19 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
           store_row(pv(p).Lc, sh.TM, t, L);
           // atan2(sin h, cos h) of the reference (:401-405) only wraps h into (-pi, pi]: done arithmetically
           v = L.h - 6.28318530717958647692f * rintf(L.h * 0.15915494309189533577f);
+#ifdef GLAMR_GRECON_WIDE
+          // heading_type 'vec' (:403-405): the residual vector goes onto the prior row's (cos, sin) slots, rows e >= 1 through the mask, and
+          // vec_to_heading takes the angle of the sum -- nothing normalised; the scalar entry's row value above is replaced
+          if constexpr (x_on) if (x_vec) {
+            const int e = t - c.fr_start;
+            const float* pr = c.prior + (size_t)e * 11;
+            const float* r = x_hv + ((size_t)p * x_TB + e) * 2;
+            const float mk = e == 0 ? 1.0f : (c.dheading_mask ? c.dheading_mask[e] : 0.0f);
+            const float h = rm::atan2s(pr[10] + mk * r[1], pr[9] + mk * r[0]);
+            pv(p).Lc[9 * sh.TM + t] = h;
+            v = h;      // (already in [-pi, pi])
+          }
+#endif
         }
         if (REG_ANY) th_r[0] = v; else pv(p).theta[t] = v;
       }
@@ -1951,6 +1993,40 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
           const bool first = e == 0;
           const int i = first ? lo.local_heading : lo.local_dheading + e;
           const bool upd = first ? (bool)(st.var_mask & GLAMR_VAR_LOCAL_HEADING) : (bool)(st.var_mask & GLAMR_VAR_LOCAL_DHEADING);
+#ifdef GLAMR_GRECON_WIDE
+          // heading_type 'vec': the angle's gradient goes through vec_to_heading (atan2s) at the summed vector onto the row's two residual numbers,
+          // rows e >= 1 through the mask; the regularisers are on the variable itself (no mask, rows e >= 1).  The scalar entry is not touched.
+          if constexpr (x_on) if (x_vec) {
+            const size_t hi = (size_t)p * x_TB + e;
+            float* hr = x_hv + hi * 2;
+            float* hw = x_hvws + hi * GLAMR_EXT_HV_WS;
+            const float* pr = c.prior + (size_t)e * 11;
+            const float pc = pr[9], psn = pr[10];
+            const float mk = first ? 1.0f : (c.dheading_mask ? c.dheading_mask[e] : 0.0f);
+            AdamRegs<2> a_v;
+            a_v.zero();
+            if (upd) a_v.load(hr, hw, hw + 2, 0); else for (int k = 0; k < 2; ++k) a_v.P[k] = hr[k];
+            float gy = 0.f, gx = 0.f;
+            rm::atan2s_bwd(psn + mk * a_v.P[1], pc + mk * a_v.P[0], gh, gy, gx);
+            float gv[2] = {mk * gx, mk * gy};
+            if (!first) {
+              const float w_r = (((x_hvl >> GLAMR_EXT_HV_LOSS_DHEADING_REG) & 1u) && !((x_hvmon >> GLAMR_EXT_HV_LOSS_DHEADING_REG) & 1u)) ? sx->hv_weight[GLAMR_EXT_HV_LOSS_DHEADING_REG] / n_exist_m1 : 0.f;
+              const float w_n = (((x_hvl >> GLAMR_EXT_HV_LOSS_DHEADING_REG_NEW) & 1u) && !((x_hvmon >> GLAMR_EXT_HV_LOSS_DHEADING_REG_NEW) & 1u)) ? sx->hv_weight[GLAMR_EXT_HV_LOSS_DHEADING_REG_NEW] / n_exist_m1 : 0.f;
+              for (int k = 0; k < 2; ++k) {
+                const float r = a_v.P[k] * FPS;
+                float sv, cv;
+                rm::sincos_(a_v.P[k], sv, cv);
+                const float a = (cv - 1.0f) * FPS, b = sv * FPS;
+                if (last) { if ((x_hvl >> GLAMR_EXT_HV_LOSS_DHEADING_REG) & 1u) hvsum[GLAMR_EXT_HV_LOSS_DHEADING_REG] += r * r;
+                            if ((x_hvl >> GLAMR_EXT_HV_LOSS_DHEADING_REG_NEW) & 1u) hvsum[GLAMR_EXT_HV_LOSS_DHEADING_REG_NEW] += a * a + b * b; }
+                gv[k] += 2.0f * FPS * r * w_r + 2.0f * FPS * FPS * ((cv - 1.0f) * (-sv) + sv * cv) * w_n;
+              }
+            }
+            if (x_hvg) { x_hvg[hi * 2 + 0] = gv[0]; x_hvg[hi * 2 + 1] = gv[1]; }
+            if (upd) a_v.step_store(hr, hw, hw + 2, nullptr, 0, gv, ac);
+            continue;
+          }
+#endif
           AdamRegs<1> a_h = a_hpre;
           if (!REG_ANY) { if (upd) a_h.load(s.p, s.m, s.v, i); else a_h.P[0] = s.p[i]; }
           float gj[1] = {gh};
@@ -2014,6 +2090,24 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
         float xt[GLAMR_EXT_NUM_LOSSES];
         for (int i = 0; i < GLAMR_EXT_NUM_LOSSES; ++i) xt[i] = rt.reduce_sum(xsum[i]);
         if (rt.tid() == 0) for (int i = 0; i < GLAMR_EXT_NUM_LOSSES; ++i) glob(sx->losses)[i] = xt[i] / (float)(P * T);
+        if (x_vec && sx->hv_losses) {      // (same block reduction as every other value: one fixed order of additions)
+          if (!update)      // a forward-only launch has no phase J: the values from the variable, rows e >= 1
+            for (int p = 0; p < P; ++p) {
+              const int n = pv(p).fr_end - pv(p).fr_start;
+              for (int e = rt.tid() + 1; e < n; e += rt.nthreads())
+                for (int k = 0; k < 2; ++k) {
+                  const float x = x_hv[((size_t)p * x_TB + e) * 2 + k], r = x * FPS;
+                  float sv, cv;
+                  rm::sincos_(x, sv, cv);
+                  const float a = (cv - 1.0f) * FPS, b = sv * FPS;
+                  if ((x_hvl >> GLAMR_EXT_HV_LOSS_DHEADING_REG) & 1u) hvsum[GLAMR_EXT_HV_LOSS_DHEADING_REG] += r * r;
+                  if ((x_hvl >> GLAMR_EXT_HV_LOSS_DHEADING_REG_NEW) & 1u) hvsum[GLAMR_EXT_HV_LOSS_DHEADING_REG_NEW] += a * a + b * b;
+                }
+            }
+          float ht[GLAMR_EXT_HV_NUM_LOSSES];
+          for (int i = 0; i < GLAMR_EXT_HV_NUM_LOSSES; ++i) ht[i] = rt.reduce_sum(hvsum[i]);
+          if (rt.tid() == 0) for (int i = 0; i < GLAMR_EXT_HV_NUM_LOSSES; ++i) glob(sx->hv_losses)[i] = ((x_hvl >> i) & 1u) ? ht[i] / n_exist_m1 : 0.f;
+        }
       }
 #endif
     }
@@ -2027,6 +2121,8 @@ GLAMR_HD void run_scene(RT& rt, Scene& sc, const glamr_stage_desc& st, const gla
 #ifdef GLAMR_GRECON_WIDE
     if constexpr (x_on) if (FAST == 0 && hist && sx->hist && rt.tid() == 0)
       for (int k = 0; k < GLAMR_EXT_NUM_LOSSES; ++k) glob(sx->hist)[(size_t)it * GLAMR_EXT_NUM_LOSSES + k] = glob(sx->losses)[k];
+    if constexpr (x_on) if (FAST == 0 && hist && x_vec && sx->hv_hist && sx->hv_losses && rt.tid() == 0)
+      for (int k = 0; k < GLAMR_EXT_HV_NUM_LOSSES; ++k) glob(sx->hv_hist)[(size_t)it * GLAMR_EXT_HV_NUM_LOSSES + k] = glob(sx->hv_losses)[k];
 #endif
   };
   // GLAMR_FLAG_NO_REPORT (launch-by-launch schedules: the gradient launch of every iteration but a stage's last): the final evaluation is an

@@ -285,8 +285,19 @@ class GlobalReconOptimizer:
                      'flag_opt_person2cam_trans'):
             if g(flag, False):
                 raise NotImplementedError('%s is not supported by the MI355X path' % flag)
-        if g('heading_type', 'scalar') != 'scalar' or not g('flag_cam_inv_trans_res_all', True) or not g('flag_opt_cam', True):
-            raise NotImplementedError('unsupported grecon_model_specs')
+        if not g('flag_cam_inv_trans_res_all', True):
+            raise NotImplementedError('flag_cam_inv_trans_res_all = False in grecon_model_specs is not supported')
+        if not g('flag_opt_cam', True):
+            raise NotImplementedError('flag_opt_cam = False in grecon_model_specs is not supported')
+        # heading_type 'vec' (:191-193, 403-405): traj_local_heading (2,) and traj_local_dheading (len - 1, 2) are added to the (cos, sin)
+        # slots of the prior rows before vec_to_heading.  They live in PackedScenes.t['heading_vec'], every stage launch (the 'init' forward passes
+        # included) carries a glamr_stage_ext that points at it, and the variable's two regularisers are taken off every stage's loss_cfg here and
+        # run in that extension.  heading_vec_loss_history[stage]: (scenes, iterations, 2) UNWEIGHTED values, with a log / keep_loss_history.
+        self.heading_vec = packing.is_heading_vec(self.specs)
+        self._heading_cfg = {}
+        self.heading_vec_loss_history = {}
+        if self.heading_vec:
+            self.opt_stage_specs, self._heading_cfg = packing.split_heading_vec_specs(self.opt_stage_specs)
         # latent-optimisation mode (:43-44,155-158,434-437,619-622): the priors run INSIDE the Adam loop and the latent draws are parameters
         self.flag_opt_motion_latent = bool(g('flag_opt_motion_latent', False))
         self.flag_opt_traj_latent = bool(g('flag_opt_traj_latent', False))
@@ -334,6 +345,15 @@ class GlobalReconOptimizer:
                               (self.flag_opt_vis_local_rot, 'flag_opt_vis_local_rot'), (bool(g('absolute_heading', False)), 'absolute_heading')):
                 if on:
                     raise NotImplementedError('%s together with %s is not supported' % (what, other))
+        if self.heading_vec:
+            # (the VJP kernels, glamr_grecon_aux_step and the launch-by-launch schedules read the scalar heading entries, which are dead here)
+            for on, other in ((bool(g('flag_attach_traj_pred', False)), 'flag_attach_traj_pred'),
+                              (bool(g('flag_opt_motion_latent', False) or g('flag_opt_traj_latent', False)), 'the latent-optimisation mode'),
+                              (bool(self._pen_cfg), 'the penetration term (loss_cfg)'), (bool(self._aux_cfg), self._aux_what() if self._aux_cfg else ''),
+                              (bool(g('flag_aux_on_device', False)), 'flag_aux_on_device'),
+                              (self.flag_opt_vis_local_rot, 'flag_opt_vis_local_rot'), (bool(g('absolute_heading', False)), 'absolute_heading')):
+                if on:
+                    raise NotImplementedError("heading_type = 'vec' together with %s is not supported" % other)
         if self._off_kernel_term() is not None:
             extra_loss_schedule.check_supported(self.specs, what=self._off_kernel_term())
         elif self._aux_on_device():
@@ -364,10 +384,14 @@ class GlobalReconOptimizer:
             if getattr(self, '_world_cfg', None):
                 raise NotImplementedError('extra_loss together with world_dxy / world_res / traj_rot_res / traj_trans_res (the world-frame residuals) is not '
                                           'supported: glamr_grecon_pose_backward does not know the residuals')
+            if getattr(self, 'heading_vec', False):
+                raise NotImplementedError("extra_loss together with heading_type = 'vec' is not supported: glamr_grecon_pose_backward reads the scalar "
+                                          'heading entries')
             extra_loss_schedule.check_supported(self.specs)
         self._extra_loss = fn
 
     flag_aux_on_device = False      # (the default of grecon_model_specs.flag_aux_on_device, also for an optimiser that never ran __init__)
+    heading_vec, _heading_cfg = False, {}      # (heading_type 'scalar', likewise)
 
     def _aux_what(self):
         return extra_loss_schedule.aux_what({n for c in self._aux_cfg.values() for n in c})
@@ -521,8 +545,8 @@ class GlobalReconOptimizer:
             n = int(d['exist_len'])
             d['traj_local_xy'] = np.zeros(2, np.float32)
             d['traj_local_dxy'] = np.zeros((n - 1, 2), np.float32)
-            d['traj_local_heading'] = np.zeros(1, np.float32)
-            d['traj_local_dheading'] = np.zeros(n - 1, np.float32)
+            d['traj_local_heading'] = np.zeros(2 if self.heading_vec else 1, np.float32)      # (:191-193)
+            d['traj_local_dheading'] = np.zeros((n - 1, 2) if self.heading_vec else n - 1, np.float32)
             d['traj_local_z'] = np.zeros(n, np.float32)
             d['traj_local_rot'] = np.zeros((n, 6), np.float32)
         ids = list(persons.keys())
@@ -629,7 +653,7 @@ class GlobalReconOptimizer:
             j_locals[si][idx] = jl[off:off + d['max_len']]
             off += d['max_len']
         # first world trajectory + (optionally) the all-frames camera, then the 'init' forward pass (:241-246)
-        packed = packing.PackedScenes(datas, j_locals, dev, self.cam_fix_frames)
+        packed = packing.PackedScenes(datas, j_locals, dev, self.cam_fix_frames, heading_vec=self.heading_vec)
         self._run(packed, self._forward_only_desc())
         if self.flag_init_cam_all_frames:
             h = packed.fetch(('orient_world', 'trans_world'))
@@ -845,6 +869,7 @@ class GlobalReconOptimizer:
             if gate is not None and not prep_early:
                 gate.before(torch.cuda.current_stream(dev))
         packed = packing.PackedScenes.empty(S, P, T, dev, seq_names=[str(m['seq_name']) for m in rin.meta])
+        packed.heading_vec = self.heading_vec      # (heading_type 'vec': zeros of their own, made with the first launch's extension)
         packed.person_ids = rin.ids
         packed.t['cam_K'] = g['K']
         packed.t['n_persons'] = rin.n_persons
@@ -942,8 +967,10 @@ class GlobalReconOptimizer:
         src.update({'pa_' + k: v for k, v in packed.person_arrays.items() if k not in ('nets_pose', 'nets_vis')})
         if 'rel_transform_cam' in packed.t:
             src['rel'] = packed.t['rel_transform_cam']
-        if 'world_res' in packed.t:
+        if 'world_res' in packed.t and (packed.has_world_dxy or packed.world_res_listed):      # (a 'vec' run has the array for its extension's launches: not reported, not copied)
             src['world_res'] = packed.t['world_res']
+        if packed.heading_vec:
+            src['heading_vec'] = packed.heading_vec_arrays()
         ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
         host = {}
         rin = packed.keepalive[0] if packed.keepalive else None
@@ -995,6 +1022,8 @@ class GlobalReconOptimizer:
             var = lambda name: (lambda: packing.person_view(h['params'][si], l, pi, name)[packing.var_rows(name, n, Ts)])
             cut = {name: var(name) for name in packing.PERSON_VARS}
             cut.update({key: (lambda key=key: h['world_res'][k, :Ts, packing.WORLD_KEYS[key]]) for key in world_keys})
+            if 'heading_vec' in h:      # heading_type 'vec': (2,) and (len - 1, 2)
+                cut.update({'traj_local_heading': lambda: h['heading_vec'][k, 0], 'traj_local_dheading': lambda: h['heading_vec'][k, 1:n]})
             cut.update({
                 'smpl_pose': frame('pa_smpl_pose'), 'smpl_beta': frame('pa_smpl_beta'), 'smpl_orient_cam': frame('orient_cam'), 'root_trans_cam': frame('pa_trans_cam'),
                 'cam_K': lambda: h['cam_K'][k, :Ts].reshape(Ts, 3, 3), 'traj_local_pred': lambda: h['traj_local_pred'][k, :n],
@@ -1079,7 +1108,10 @@ class GlobalReconOptimizer:
         return sd
 
     def _run(self, packed, sd):
-        stepwise.run_stage(packed, sd, False)
+        ext = None
+        if packed.heading_vec:      # (a forward pass of a heading_type 'vec' batch: the extension's instances, without a term)
+            ext, _ = packing.world_ext(stepwise.world_stage(packed, None), packed, niters=int(sd.niters), heading={})
+        stepwise.run_stage(packed, sd, False, ext=ext)
         return packed.last_ws
 
     @staticmethod
@@ -1102,25 +1134,30 @@ class GlobalReconOptimizer:
             if want_hist and sd.niters > 0:
                 packed.t['loss_history'] = torch.zeros((packed.S, int(sd.niters), len(packing.LOSS_IDS)), dtype=torch.float32, device=self.device)
             world = stepwise.world_stage(packed, self._world_cfg.get(stage))
-            if world is None:
+            if packed.heading_vec != self.heading_vec:
+                raise ValueError("the batch was packed with heading_type = %r, the optimiser has %r" % tuple('vec' if v else 'scalar' for v in (packed.heading_vec, self.heading_vec)))
+            heading = self._heading_cfg[stage] if self.heading_vec else None
+            if world is None and heading is None:
                 events.append(self._run(packed, sd))               # the launch's workspace: its header carries the kernel's own clock stamps
-                whist = None
+                whist = hhist = None
             else:
                 if packed.t.get('frozen') is not None:
-                    raise NotImplementedError('world_dxy / world_res / traj_rot_res / traj_trans_res (the world-frame residuals) on a person-sharded batch')
-                ext, keep = packing.world_ext(world, packed, niters=int(sd.niters), want_hist='loss_history' in packed.t)
+                    raise NotImplementedError("world_dxy / world_res / traj_rot_res / traj_trans_res (the world-frame residuals) or heading_type = 'vec' on a person-sharded batch")
+                ext, keep = packing.world_ext(world, packed, niters=int(sd.niters), want_hist='loss_history' in packed.t, heading=heading)
                 stepwise.run_stage(packed, sd, False, ext=ext)
                 events.append(packed.last_ws)
-                stepwise.end_world_stage(packed, world, keep)
-                whist = keep.get('loss_history')
+                if world is not None:
+                    stepwise.end_world_stage(packed, world, keep)
+                packed.heading_vec_losses = keep.get('hv_losses')
+                whist, hhist = keep.get('loss_history') if world is not None else None, keep.get('hv_loss_history')
             if 'loss_history' in packed.t:
-                self._report_stage(packed, stage, spec, packed.t.pop('loss_history'), events[-1], whist, (world or {}).get('loss_order'))
+                self._report_stage(packed, stage, spec, packed.t.pop('loss_history'), events[-1], whist, (heading or world or {}).get('loss_order'), hhist)
             has_wd = stepwise.end_stage(packed, spec, has_wd)
         packed.has_world_dheading = has_wd
         packed.stage_ws = events
         return packed
 
-    def _report_stage(self, packed, stage, spec, hist, ws, world_hist=None, loss_order=None):
+    def _report_stage(self, packed, stage, spec, hist, ws, world_hist=None, loss_order=None, heading_hist=None):
         """write_logs (:646-659) for every iteration of a finished stage launch: `cfg id - sequence - stage | it/niters | TE: .. ETA: .. | LR: .. |
         term: value | ...` with the UNWEIGHTED values (loss_uw_dict, :564) of the stage's terms in the order of its loss_cfg.  The time per
         iteration is the launch's duration divided by its iterations."""
@@ -1130,13 +1167,17 @@ class GlobalReconOptimizer:
         wh = world_hist.cpu().numpy() if world_hist is not None else None
         if wh is not None:
             self.world_loss_history[stage] = wh
+        hh = heading_hist.cpu().numpy() if heading_hist is not None else None
+        if hh is not None:
+            self.heading_vec_loss_history[stage] = hh
         if self.log is None:
             return
         n_it = h.shape[1]
         it_secs = self.launch_ms(ws) * 1e-3 / max(1, n_it)
         hms = lambda secs: str(datetime.timedelta(seconds=round(secs)))
-        names = [n for n in (loss_order or spec['loss_cfg']) if n in packing.LOSS_IDS or (wh is not None and n in packing.WORLD_TERMS)]
-        value = lambda si, it, n: h[si, it, packing.LOSS_IDS[n]] if n in packing.LOSS_IDS else wh[si, it, packing.WORLD_TERMS[n]]
+        hv_terms = packing.HEADING_VEC_TERMS if hh is not None else {}      # (a 'vec' run: both of the variable's terms are the extension's)
+        names = [n for n in (loss_order or spec['loss_cfg']) if n in hv_terms or n in packing.LOSS_IDS or (wh is not None and n in packing.WORLD_TERMS)]
+        value = lambda si, it, n: hh[si, it, hv_terms[n]] if n in hv_terms else h[si, it, packing.LOSS_IDS[n]] if n in packing.LOSS_IDS else wh[si, it, packing.WORLD_TERMS[n]]
         for si in range(packed.S):
             head = '%s - %s - %s' % (self.cfg_id, packed.seq_names[si], stage)
             for it in range(n_it):
@@ -1436,7 +1477,7 @@ class GlobalReconOptimizer:
                 with torch.no_grad():
                     jl[idx] = self.smpl(global_orient=z, body_pose=pose, betas=beta, root_trans=z, return_verts=False).joints.cpu()
             j_locals.append(jl)
-        packed = packing.PackedScenes(datas, j_locals, self.device, self.cam_fix_frames)
+        packed = packing.PackedScenes(datas, j_locals, self.device, self.cam_fix_frames, heading_vec=self.heading_vec)
         has_wd = any('world_dheading' in pd for d in datas for pd in d['person_data'].values())
         self._run_schedule_or_extra(packed, max_iters, has_wd=has_wd)
         return self.collect(datas, packed)

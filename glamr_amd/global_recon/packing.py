@@ -159,9 +159,55 @@ def split_world_specs(opt_stage_specs):
     return (rest if world else opt_stage_specs), world
 
 
-def world_ext(world, packed, niters=0, want_grads=False, want_hist=False):
+# Vector headings: grecon_model_specs heading_type = 'vec' (global_recon_model.py:191-193, 403-405).  The variables
+# traj_local_heading (2,) / traj_local_dheading (len - 1, 2) live in PackedScenes.t['heading_vec'] (S * P, T, 2), row 0 and rows e >= 1 of a slot;
+# the entries local_heading / local_dheading of the params row are dead.  Both regularisers of the variable run in the extension, in the order of
+# GLAMR_EXT_HV_LOSS_*: local_traj_dheading_reg (otherwise one of AUX_LOSS_IDS) and local_traj_dheading_reg_new (otherwise the fused term of LOSS_IDS).
+HEADING_VEC_TERMS = {'local_traj_dheading_reg': 0, 'local_traj_dheading_reg_new': 1}
+HEADING_VEC_WS_FLOATS = 4
+HEADING_VEC_KEYS = ('traj_local_heading', 'traj_local_dheading')
+
+
+def is_heading_vec(model_specs):
+    ht = model_specs.get('heading_type', 'scalar')
+    if ht not in ('scalar', 'vec'):
+        raise NotImplementedError("heading_type %r in grecon_model_specs is not supported ('scalar' or 'vec')" % (ht,))
+    return ht == 'vec'
+
+
+def split_heading_vec(spec):
+    """A stage's spec of a heading_type = 'vec' run -> (the spec without the names of HEADING_VEC_TERMS -- what split_off_kernel, split_world and
+    stage_desc are given --, dict(terms={name: dict(weight, monitor_only)} in loss_cfg's order, loss_order=[every name of the stage's loss_cfg]))."""
+    terms = {}
+    for n, c in spec['loss_cfg'].items():
+        if n in HEADING_VEC_TERMS:
+            if c.get('rot_type', '6d') != '6d' or c.get('first_frame_trans_only', False):
+                raise NotImplementedError('loss option not supported: %s %s' % (n, c))
+            terms[n] = dict(weight=float(c['weight']), monitor_only=bool(c.get('monitor_only', False)))
+    rest = dict(spec, loss_cfg={n: c for n, c in spec['loss_cfg'].items() if n not in HEADING_VEC_TERMS})
+    heading = dict(terms=terms, loss_order=list(spec['loss_cfg']))
+    rest['heading_vec'] = heading      # (a schedule that is handed the stripped specs and cannot run vector headings sees that: has_heading_vec)
+    return rest, heading
+
+
+def has_heading_vec(opt_stage_specs):
+    """Whether a schedule's specs are those of a heading_type = 'vec' run (split_heading_vec marked them)."""
+    return any(spec.get('heading_vec') is not None for spec in opt_stage_specs.values())
+
+
+def split_heading_vec_specs(opt_stage_specs):
+    """opt_stage_specs of a heading_type = 'vec' run -> (the specs without the two regularisers, {stage: split_heading_vec's second result})."""
+    rest, heading = {}, {}
+    for stage, spec in opt_stage_specs.items():
+        rest[stage], heading[stage] = split_heading_vec(spec)
+    return rest, heading
+
+
+def world_ext(world, packed, niters=0, want_grads=False, want_hist=False, heading=None):
     """split_world's second result (or None: a stage that only carries an existing world_dxy along) -> glamr_stage_ext on `packed`'s residual
-    arrays (packed.world_arrays makes them), and the tensors it points at beside the residuals: dict(losses, ws[, grads][, loss_history])."""
+    arrays (packed.world_arrays makes them), and the tensors it points at beside the residuals: dict(losses, ws[, grads][, loss_history]).
+    `heading`: split_heading_vec's second result (or {}: a forward pass) of a heading_type = 'vec' batch -- the descriptor then also carries
+    packed.heading_vec_arrays() with hv_ws, hv_losses[, hv_grads][, hv_loss_history]; None: those fields stay zero, the call is what it was."""
     world = world or dict(variables=[], terms={})
     ex = _lib.StageExt()
     ex.var_mask = 0
@@ -191,6 +237,30 @@ def world_ext(world, packed, niters=0, want_grads=False, want_hist=False):
     for name in ('losses', 'grads', 'loss_history'):
         setattr(ex, name, ctypes.c_void_p(keep[name].data_ptr()) if name in keep else None)
     ex.workspace = ctypes.c_void_p(keep['ws'].data_ptr())
+    if heading is not None:
+        if not packed.heading_vec:
+            raise ValueError("vector headings on a batch that was not packed with heading_type = 'vec'")
+        hv = packed.heading_vec_arrays()
+        hv_floats = _lib.lib().glamr_grecon_heading_vec_workspace_bytes(S, packed.P, packed.T) // 4
+        assert hv_floats == hv.shape[0] * hv.shape[1] * HEADING_VEC_WS_FLOATS, 'glamr_grecon_heading_vec_workspace_bytes and packing.HEADING_VEC_WS_FLOATS disagree'
+        keep['hv_ws'] = torch.empty(hv_floats, dtype=torch.float32, device=dev).view(hv.shape[:2] + (HEADING_VEC_WS_FLOATS,))
+        keep['hv_losses'] = torch.zeros((S, len(HEADING_VEC_TERMS)), dtype=torch.float32, device=dev)
+        if want_grads:
+            keep['hv_grads'] = torch.zeros_like(hv)
+        if want_hist and niters > 0:
+            keep['hv_loss_history'] = torch.zeros((S, int(niters), len(HEADING_VEC_TERMS)), dtype=torch.float32, device=dev)
+        ex.hv_loss_mask = ex.hv_monitor_mask = 0
+        for name, c in (heading.get('terms') or {}).items():
+            i = HEADING_VEC_TERMS[name]
+            ex.hv_loss_mask |= 1 << i
+            ex.hv_loss_weight[i] = c['weight']
+            if c['monitor_only']:
+                ex.hv_monitor_mask |= 1 << i
+        ex.heading_vec = ctypes.c_void_p(hv.data_ptr())
+        ex.heading_vec_workspace = ctypes.c_void_p(keep['hv_ws'].data_ptr())
+        ex.heading_vec_grads = ctypes.c_void_p(keep['hv_grads'].data_ptr()) if 'hv_grads' in keep else None
+        ex.hv_losses = ctypes.c_void_p(keep['hv_losses'].data_ptr())
+        ex.hv_loss_history = ctypes.c_void_p(keep['hv_loss_history'].data_ptr()) if 'hv_loss_history' in keep else None
     return ex, keep
 
 
@@ -364,6 +434,15 @@ class PackedScenes:
         # from the first stage that lists it on, like has_world_dheading; the residual tensors are reported once a stage listed world_res or a term
         self.has_world_dxy = self.world_res_listed = False
         self.world_losses = None        # (S, 2) on the device: traj_rot_res, traj_trans_res of the last stage that ran with the extension
+        # heading_type = 'vec': the batch's heading variables are t['heading_vec'] (heading_vec_arrays) and every launch carries the extension
+        self.heading_vec = False
+        self.heading_vec_losses = None  # (S, 2) on the device: local_traj_dheading_reg, local_traj_dheading_reg_new of the last stage
+
+    def heading_vec_arrays(self):
+        """t['heading_vec']: (S * P, T, 2) by EXISTING row -- row 0 traj_local_heading, row e >= 1 traj_local_dheading[e - 1]; zeros when first asked for."""
+        if 'heading_vec' not in self.t:
+            self.t['heading_vec'] = torch.zeros((self.S * self.P, self.T, 2), dtype=torch.float32, device=self.device)
+        return self.t['heading_vec']
 
     def world_arrays(self):
         """t['world_res']: (S * P, T, 8) world_dxy | smpl_orient_world_res | root_trans_world_res by video frame, zeros when first asked for."""
@@ -394,9 +473,10 @@ class PackedScenes:
         self.has_world_dheading = False
         return self
 
-    def __init__(self, datas, j_locals, device, cam_fix_frames=((0, None),)):
+    def __init__(self, datas, j_locals, device, cam_fix_frames=((0, None),), heading_vec=False):
         """datas: list of `data` dicts (one per sequence); j_locals: list (per scene) of dict idx -> (T,26,3) joints computed
-        with zero root orientation and zero root translation."""
+        with zero root orientation and zero root translation.  heading_vec: grecon_model_specs heading_type = 'vec' -- traj_local_heading is (2,)
+        and traj_local_dheading (len - 1, 2); shapes that disagree with it raise ValueError."""
         S = len(datas)
         self.person_ids = [list(d['person_data'].keys()) for d in datas]
         P = max(len(ids) for ids in self.person_ids)
@@ -423,6 +503,7 @@ class PackedScenes:
         rtc = f32(S * P, T, 3) if all('root_trans_cam' in pd for d in datas for pd in d['person_data'].values()) else None
         # a continued optimisation resumes from the world-frame residuals an earlier run returned (world_dxy exists from then on)
         world = f32(S * P, T, EXT_FLOATS) if any(k in pd for d in datas for pd in d['person_data'].values() for k in WORLD_KEYS) else None
+        hvec = f32(S * P, T, 2) if heading_vec else None
         for si, d in enumerate(datas):
             ids = self.person_ids[si]
             Ts = int(d['seq_len'])
@@ -463,7 +544,18 @@ class PackedScenes:
                     for (s, e) in cam_fix_frames:
                         m[s:e] = 0.0
                     t['dheading_mask'][slot, 1:n] = m
+                h0, dh = cpu(pd['traj_local_heading']), cpu(pd['traj_local_dheading'])
+                want = ((2,), (n - 1, 2)) if heading_vec else ((1,), (n - 1,))
+                is_vec = tuple(h0.shape) == (2,) and tuple(dh.shape) == (n - 1, 2)
+                if is_vec != bool(heading_vec):
+                    raise ValueError("traj_local_heading %s / traj_local_dheading %s of person %r do not fit heading_type = %r (%s / %s): a result of one "
+                                     "heading_type cannot be continued under the other"
+                                     % (tuple(h0.shape), tuple(dh.shape), idx, 'vec' if heading_vec else 'scalar', want[0], want[1]))
+                if heading_vec:
+                    hvec[slot, 0], hvec[slot, 1:n] = h0.float(), dh.float()
                 for name in PERSON_VARS:
+                    if heading_vec and name in HEADING_VEC_KEYS:
+                        continue      # (the scalar entries of the params row are dead)
                     if name != 'world_dheading' or name in pd:
                         person_view(prm, l, pi, name)[var_rows(name, n, Ts)] = cpu(pd[name])
             if P > 1 and d.get('rel_transform_cam'):
@@ -481,6 +573,9 @@ class PackedScenes:
                 jl[si * P + pi, :int(d['seq_len'])] = j_locals[si][idx] if on_device else cpu(j_locals[si][idx]).float()
         self.t['j_local'] = jl if on_device else jl.contiguous().to(device)
         self.has_world_dheading = any('world_dheading' in pd for d in datas for pd in d['person_data'].values())
+        if hvec is not None:
+            self.heading_vec = True
+            self.t['heading_vec'] = hvec.to(device)
         if world is not None:
             self.t['world_res'] = world.to(device)
             self.has_world_dxy = any('world_dxy' in pd for d in datas for pd in d['person_data'].values())
@@ -516,6 +611,7 @@ class PackedScenes:
         h = self.fetch()
         world = self.t['world_res'].detach().cpu().numpy() if 'world_res' in self.t else None
         world_keys = [k for k in WORLD_KEYS if world is not None and (self.has_world_dxy if k == 'world_dxy' else self.world_res_listed)]
+        hvec = self.heading_vec_arrays().detach().cpu().numpy() if self.heading_vec else None
         conv = (lambda a: torch.from_numpy(np.ascontiguousarray(a))) if as_torch else (lambda a: np.ascontiguousarray(a))
         var = set(stage_specs['opt_variables']) if stage_specs is not None else set()
         for si, d in enumerate(datas):
@@ -542,6 +638,8 @@ class PackedScenes:
                 for name in PERSON_VARS:
                     if name != 'world_dheading' or name in var or name in pd:
                         pd[name] = conv(person_view(prm, l, pi, name)[var_rows(name, n, Ts)])
+                if hvec is not None:      # heading_type = 'vec': (2,) and (len - 1, 2), from the array of their own
+                    pd['traj_local_heading'], pd['traj_local_dheading'] = conv(hvec[slot, 0]), conv(hvec[slot, 1:n])
                 for key in world_keys:
                     pd[key] = conv(world[slot, :Ts, WORLD_KEYS[key]])
                 pd['smpl_orient_world'] = conv(h['orient_world'][slot, :Ts])

@@ -192,6 +192,9 @@ class PersonShardedSchedule:
         if packing.has_world(opt_stage_specs) or getattr(packed, 'has_world_dxy', False):      # (a model's opt_stage_specs have the names taken off and say so)
             raise NotImplementedError('world_dxy / world_res / traj_rot_res / traj_trans_res (the world-frame residuals) in a person-sharded run is not '
                                       'supported: the schedule makes its own Adam steps on `params`, which does not hold them')
+        if packing.has_heading_vec(opt_stage_specs) or model_specs.get('heading_type', 'scalar') != 'scalar' or getattr(packed, 'heading_vec', False):
+            raise NotImplementedError("heading_type = 'vec' in a person-sharded run is not supported: the schedule makes its own Adam steps on `params`, "
+                                      'whose heading entries are dead with vector headings')
         own = self.owned(P)
         block = -(-P // self.world)
         frozen = torch.ones((S, P), dtype=torch.int32)

@@ -425,8 +425,32 @@ typedef struct glamr_stage_ext {
   float* losses;                         /* dev (n_scenes, GLAMR_EXT_NUM_LOSSES) unweighted values of the LAST evaluation (a term not in loss_mask: 0) */
   float* loss_history;                   /* dev (n_scenes, stage->niters, GLAMR_EXT_NUM_LOSSES) or NULL; read only when batch->loss_history is recorded */
   void* workspace;                       /* dev, glamr_grecon_ext_workspace_bytes: Adam moments and the pose before the residual */
+  /* heading_type = 'vec' (below).  heading_vec == NULL: none of these is read, and the call is what it was before they existed. */
+  float* heading_vec;                    /* dev (slots, max_len, 2) in/out: row 0 traj_local_heading, row e >= 1 traj_local_dheading[e - 1] (cos slot, sin slot) */
+  float* heading_vec_grads;              /* dev, same shape, or NULL: the gradient of the LAST evaluated iteration, rows e < exist_len (others untouched) */
+  void* heading_vec_workspace;           /* dev, glamr_grecon_heading_vec_workspace_bytes: Adam's moments */
+  uint32_t hv_loss_mask, hv_monitor_mask;      /* bit GLAMR_EXT_HV_LOSS_* */
+  float hv_loss_weight[2];
+  float* hv_losses;                      /* dev (n_scenes, GLAMR_EXT_HV_NUM_LOSSES) unweighted values of the LAST evaluation, or NULL when hv_loss_mask == 0 */
+  float* hv_loss_history;                /* dev (n_scenes, stage->niters, GLAMR_EXT_HV_NUM_LOSSES) or NULL; as loss_history */
 } glamr_stage_ext;
 size_t glamr_grecon_ext_workspace_bytes(int n_scenes, int max_persons, int max_len);
+/* Vector headings: grecon_model_specs heading_type = 'vec' of the reference (global_recon_model.py:191-193, 403-405).  The optimised heading
+ * variables are 2-vectors added to the (cos, sin) slots of the prior row BEFORE vec_to_heading, nothing normalised: for existing row e of a person,
+ * with m_0 = 1, m_e = dheading_mask[e] (NULL mask: 0), prior row pr and r_e = heading_vec[slot][e],
+ *     h_e = atan2s(pr[10] + m_e r_e[1], pr[9] + m_e r_e[0]);        g(r_e) = m_e (gx, gy),  (gy, gx) = atan2s_bwd(y, x, g(h_e)).
+ * Everything after the per-row heading angle is unchanged.  In such a launch the entries local_heading / local_dheading of the params row are
+ * dead: never used (their value, NaN included, reaches no result), never updated, gradient 0 in grads_out.  GLAMR_VAR_LOCAL_HEADING / GLAMR_VAR_LOCAL_DHEADING of stage->var_mask select the
+ * update of row 0 / rows e >= 1 of heading_vec (Adam, fresh zero moments per launch, rows e < exist_len of the slots p < n_persons only).
+ * The regularisers are on the variable itself (no mask), rows e >= 1, n = sum_persons (exist_len - 1):
+ *   GLAMR_EXT_HV_LOSS_DHEADING_REG      local_traj_dheading_reg (loss_func.py:216):          sum (30 r_e[c])^2 / n
+ *   GLAMR_EXT_HV_LOSS_DHEADING_REG_NEW  local_traj_dheading_reg_new (:220-230) as the reference computes it on a (len - 1, 2) tensor, heading_to_vec
+ *                                       of each component:                                  sum [(30 (cos r_e[c] - 1))^2 + (30 sin r_e[c])^2] / n
+ * Refused (GLAMR_E_UNSUPPORTED): GLAMR_LOSS_LOCAL_DHEADING_REG_NEW in stage->loss_mask (the fused term reads the scalar entries: the caller
+ * takes the bit off and sets GLAMR_EXT_HV_LOSS_DHEADING_REG_NEW), GLAMR_FLAG_ABSOLUTE_HEADING. */
+enum { GLAMR_EXT_HV_LOSS_DHEADING_REG = 0, GLAMR_EXT_HV_LOSS_DHEADING_REG_NEW, GLAMR_EXT_HV_NUM_LOSSES };
+#define GLAMR_EXT_HV_WS 4                /* per slot and row: Adam's m (2), v (2) */
+size_t glamr_grecon_heading_vec_workspace_bytes(int n_scenes, int max_persons, int max_len);
 int glamr_grecon_run_stage_ext(const glamr_scene_batch* batch, const glamr_stage_desc* stage, const glamr_stage_ext* ext, float* grads_out,
                                void* workspace, void* stream);
 /* Duration of the last glamr_grecon_run_stage that used `workspace`, from the kernel's own clock (earliest workgroup start to latest
